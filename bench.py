@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — HRFuser backbone training step on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = forward (train-mode BN) + backward + gradient exchange + fused AdamW of the HRFuser-T nuScenes backbone
@@ -9,18 +9,31 @@ on a synthetic batch of 2 images per GPU (2x3x384x640 camera + lidar + radar; BA
 all-reduce when N > 1; weak scaling).  Everything in the timed region runs on the hand-written HIP kernels (no oracle,
 no CPU fallback).  `value` = images of all ranks / wall time of exactly K steps between two barriers (max over ranks).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes the outputs of the last timed step when --dump-outputs is given,
+and prints the JSON line.  Its fields beside the headline (`value`, `ms_per_step`):
   step_ms         per-step GPU durations of the same K steps from HIP events on the launch stream: median / p10 / p90
   finite          outputs and parameters checked for NaN / Inf after the timed steps (a non-finite run is not a result)
+  step_roofline   the whole step against its bound: eager-equivalent fp32 bytes and flops of the reference graph
+                  (SURVEY 8d / BASELINE.md section 4) over the measured step time
+
+--dump-outputs DIR writes what the last timed step computed: out0..out3 (the four NHWC output maps of the backbone),
+params (the flat parameter arena after the AdamW update) and grads (the flat gradient arena of that step), float32, as
+DIR/<name>.npy, 64 MB at most in all (an array over its share is replaced by a fixed seeded sample of its elements).  The
+inputs, weights and cotangents are seeded: the same arguments give the same inputs on every run, and the AdamW of the
+timed step runs at learning rate 0 (see build_workload), so every step starts from the same weights and the results of the
+last one agree from run to run up to the rounding of the float reductions (~1e-7 relative in the gradients).
+
+Everything else takes runs of its own and is measured only with --full (null in a plain run):
+  fwd_ms_per_img  eval forward (BN running statistics), hipGraph replay, ms per image
   eager_autograd  the route an mmdet user gets: `backbone(img, mods)` + `loss.backward()` through torch.autograd + the
                   fused AdamW, eager (no hipGraph), ms per step
   roofline        the kernel family with the LARGEST time per step (isolated per-launch durations: every distinct
                   (entry point, shape) of a step re-issued 20x back-to-back in a captured hipGraph, HIP events on the launch
                   stream): algorithmic bytes (or flops) per launch / average launch duration, against 8 TB/s resp. the
                   dense fp32 MFMA peak; `traffic` = PMC-measured fabric bytes per launch with its source stated (a
-                  separate `rocprofv3 --pmc` run kept under profiles/), or null
-  step_roofline   the whole step against its bound: eager-equivalent fp32 bytes and flops of the reference graph
-                  (SURVEY 8d / BASELINE.md section 4) over the measured step time
+                  separate `rocprofv3 --pmc` run kept under profiles/), or null; --dump-kernels (implies --full) writes its per-kernel table
+  stage_roofline, neck, extract_feat, module_graph   per-stage table, HRFPN neck, backbone + neck step, module-boundary graphs
+  sync_ab         N > 1: the A/B of the other SyncBN schedules, each in a child job of its own
   cpu_baseline    the PyTorch-CPU oracle (kind "port": bit-exact restatement of the reference backbone) timed on the host
                   cores, same workload, train forward+backward, at 8 threads and at all physical cores
 """
@@ -57,14 +70,24 @@ def parse(argv=None):
     ap.add_argument('--no-neck', action='store_true', help='skip the HRFPN neck / extract_feat timings (consumers of the 4 maps)')
     ap.add_argument('--no-eager', action='store_true', help='skip the eager torch.autograd route timing')
     ap.add_argument('--profile-steps', type=int, default=1)
-    ap.add_argument('--dump-kernels', default='', help='write the per-kernel table (JSON) to this path')
+    ap.add_argument('--dump-kernels', default='', help='write the per-kernel table (JSON) to this path (implies --full)')
     ap.add_argument('--no-sync-ab', action='store_true', help='N > 1: skip the A/B of the per-lane-communicator SyncBN schedule')
     ap.add_argument('--sync-ab-child', action='store_true', help=argparse.SUPPRESS)     # internal: the A/B child job
     ap.add_argument('--sync-ab-timeout', type=float, default=240.0)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline: eval forward, eager autograd route, roofline / per-kernel and '
+                         'per-stage tables, neck, extract_feat, CPU baseline, SyncBN schedule A/B (N > 1)')
+    ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                    help='write the outputs, parameters and gradients of the last timed step as DIR/<name>.npy (float32)')
     ap.add_argument('--backend', default=os.environ.get('HRF_BENCH_BACKEND', 'nccl'),
                     help="torch.distributed backend: 'nccl' (= RCCL, the product path) | 'gloo' (flow tests of the N > 1 path on a "
                          "box with fewer GPUs than ranks: the ranks share GPU 0, eager launches)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
+    if args.dump_kernels:
+        args.full = True                          # the per-kernel table comes from the roofline pass of a full run
+    return args
 
 
 def load_cfg(tag):
@@ -228,7 +251,7 @@ def launch_ranks(args, argv):
     if rc != 0 or line is None:
         print(f'[bench] the {n}-rank job exited with {rc}' + ('' if line is not None else ' and printed no result line'), file=sys.stderr)
         return rc if rc else 1
-    if not args.no_sync_ab and line.get('sync_ab') is None:
+    if args.full and not args.no_sync_ab and line.get('sync_ab') is None:
         line['sync_ab'] = run_sync_ab(strip_flag(argv, '--dump-kernels', True), n, args.sync_ab_timeout)
     print(json.dumps(line), flush=True)
     return 0
@@ -319,7 +342,7 @@ def supervise_rank(args, argv):
             if rank == 0:
                 line.setdefault('config', {})['attempts'] = tried
                 ab_left = budget - (time.time() - t0)
-                if not args.no_sync_ab and os.environ.get('HRF_BENCH_LAUNCHED_BY_BENCH') != '1' and line.get('sync_ab') is None:
+                if args.full and not args.no_sync_ab and os.environ.get('HRF_BENCH_LAUNCHED_BY_BENCH') != '1' and line.get('sync_ab') is None:
                     if ab_left > 2 * 60:
                         line['sync_ab'] = run_sync_ab(strip_flag(argv, '--dump-kernels', True), world,
                                                       min(args.sync_ab_timeout, (ab_left - 20) / 2))
@@ -388,8 +411,37 @@ def build_workload(args, rank, world, dev, group, force_coll):
         x = x.contiguous(memory_format=torch.channels_last)
         mods = [m.contiguous(memory_format=torch.channels_last) for m in mods]
     cots = make_cotangents(net, x, mods)
-    trainer = Trainer(net, lr=1e-3 if stf else 3e-4, group=group, world_size=world)
+    # The step is the whole training step - forward, backward, gradient exchange and the fused AdamW launch, which reads and
+    # writes the full parameter and moment arenas whatever the learning rate - at learning rate 0: every step starts from the
+    # same weights, does the same work and computes the same results.  With a learning rate > 0 on one fixed batch, AdamW turns
+    # the run-to-run rounding differences of the atomic gradient reductions (~1e-7) into sign-like updates of near-zero
+    # gradients, and two runs with the same arguments drift apart within a few steps.
+    trainer = Trainer(net, lr=0.0, group=group, world_size=world)
     return tag, cfg, stf, H, W, mc, net, B, x, mods, cots, trainer
+
+
+DUMP_BYTES = (64 << 20) - (64 << 10)      # 64 MB in all, less room for the .npy headers
+
+
+def dump_outputs(path, arrays):
+    """{name: tensor} -> path/<name>.npy as float32 (float64 stays float64), DUMP_BYTES in all.  The arrays are written from the
+    smallest up; one larger than its share of what is left becomes a fixed seeded sample of its elements (the same indices on
+    every run, in ascending order)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES
+    for k, (name, t) in enumerate(items):
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        share = left // (len(items) - k)
+        if t.numel() * t.element_size() > share:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randperm(t.numel(), generator=g)[:share // t.element_size()].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        a = t.contiguous().cpu().numpy()
+        np.save(os.path.join(path, name + '.npy'), a)
+        left -= a.nbytes
 
 
 def time_steps(args, run, world, dev):
@@ -406,7 +458,7 @@ def time_steps(args, run, world, dev):
     t0 = time.perf_counter()
     evs[0].record()
     for k in range(args.steps):
-        run()
+        last = run()
         evs[k + 1].record()
     barrier()
     dt = time.perf_counter() - t0
@@ -416,7 +468,7 @@ def time_steps(args, run, world, dev):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt)
     per = sorted(evs[k].elapsed_time(evs[k + 1]) for k in range(args.steps))
-    return dt, per
+    return dt, per, last
 
 
 def leave(world, force_coll):
@@ -473,7 +525,7 @@ def sync_ab_child(args):
         if use_graph:
             trainer.capture(x, mods, cots)
         run = trainer.replay if use_graph else (lambda: trainer.step(x, mods, cots))
-        dt, per = time_steps(args, run, world, dev)
+        dt, per, _ = time_steps(args, run, world, dev)
         trainer.check()
         res.update({'ms_per_step': round(dt / args.steps * 1e3, 4), 'images_per_sec': round(B * world * args.steps / dt, 3),
                     'launch': 'hipGraph replay' if use_graph else 'eager', 'finite': bool(torch.isfinite(eng.flat_p).all())})
@@ -487,7 +539,7 @@ def sync_ab_child(args):
                 if use_graph:
                     trainer.capture(x, mods, cots)
                 run = trainer.replay if use_graph else (lambda: trainer.step(x, mods, cots))
-                dt, per = time_steps(args, run, world, dev)
+                dt, per, _ = time_steps(args, run, world, dev)
                 res['main_lane_ms_per_step'] = round(dt / args.steps * 1e3, 4)
             except Exception as e:
                 res['main_lane_error'] = f'{type(e).__name__}: {str(e)[:200]}'
@@ -538,7 +590,7 @@ def main(argv=None):
             use_graph = False
             torch.cuda.synchronize()
     run = trainer.replay if use_graph else (lambda: trainer.step(x, mods, cots))
-    dt, per = time_steps(args, run, world, dev)
+    dt, per, last = time_steps(args, run, world, dev)
     trainer.check()                                               # a timed-out peer-to-peer SyncBN exchange is not a result
     ms_per_step = dt / args.steps * 1e3
     value = B * world * args.steps / dt
@@ -548,14 +600,18 @@ def main(argv=None):
 
     # a run that went non-finite is not a result
     eng = net._engine()
-    outs = trainer._graph_outs if use_graph else trainer.step(x, mods, cots)
+    outs = trainer._graph_outs if use_graph else last
     finite = bool(torch.isfinite(eng.flat_p).all()) and all(bool(torch.isfinite(o.t).all()) for o in outs)
     if not finite:
         raise SystemExit('[bench] non-finite parameters / outputs after the timed steps: no result')
+    if args.dump_outputs and rank == 0:
+        arrays = {f'out{i}': o.t for i, o in enumerate(outs)}
+        arrays.update(params=eng.flat_p, grads=eng.flat_g)
+        dump_outputs(args.dump_outputs, arrays)
 
     # secondary metric: eval forward ms/img (BN running stats), hipGraph replay
     fwd_ms = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             fwd_ms = profiling.time_eval_forward(net, x, mods, use_graph=not args.no_graph)
         except Exception as e:
@@ -564,7 +620,7 @@ def main(argv=None):
 
     eager = None
     module_graph = None
-    if rank == 0 and world == 1 and not force_coll and not args.no_eager:
+    if rank == 0 and world == 1 and not force_coll and args.full and not args.no_eager:
         # what `backbone(img, mods)` + `loss.backward()` costs through torch.autograd (the drop-in route an mmdet user gets):
         # with eager launches, and with the module-boundary hipGraphs (captured from the third call of a signature on)
         def autograd_route(graphs, n_warm, n_timed):
@@ -609,7 +665,7 @@ def main(argv=None):
             torch.cuda.synchronize()
 
     roof = None
-    if not args.no_roofline:          # every rank runs it (the step contains collectives when N > 1)
+    if args.full and not args.no_roofline:          # every rank runs it (the step contains collectives when N > 1)
         table = profiling.profile_step(trainer, x, mods, cots, steps=args.profile_steps)
         try:
             grouped = profiling.grouped_wgrad_report(trainer, x, mods, cots) if use_graph else None
@@ -631,7 +687,7 @@ def main(argv=None):
             roof['merged_launches'] = {'launches': issued, 'calls_carried': carried}
 
     stages = None
-    if rank == 0 and world == 1 and use_graph and not args.no_roofline and (H, W) == (384, 1248 if stf else 640):
+    if rank == 0 and world == 1 and use_graph and args.full and not args.no_roofline and (H, W) == (384, 1248 if stf else 640):
         try:
             stages = profiling.stage_table(trainer, x, mods, cots, tag, PEAK_F32_MFMA, PEAK_HBM)
         except Exception as e:
@@ -650,7 +706,7 @@ def main(argv=None):
 
     neck = None
     feat = None
-    if rank == 0 and world == 1 and not args.no_neck:
+    if rank == 0 and world == 1 and args.full and not args.no_neck:
         # the HRFPN neck that consumes the four maps, timed on its own (not part of `value`)
         try:
             widths = cfg['extra']['stage4']['num_channels']
@@ -684,7 +740,7 @@ def main(argv=None):
                 feat = {'error': str(e)[:200]}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(tag, B, H, W, mc)
 
     if rank == 0:
@@ -693,7 +749,7 @@ def main(argv=None):
             'value': round(value, 3), 'unit': 'images/sec', 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': round(ms_per_step, 4), 'higher_is_better': True,
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-            'config': {'workload': f'{tag} backbone train step (fwd+bwd+grad exchange+AdamW), {B} img/GPU, '
+            'config': {'workload': f'{tag} backbone train step (fwd+bwd+grad exchange+AdamW at lr 0), {B} img/GPU, '
                                    f'{B}x3x{H}x{W} camera + {len(mc)} modalities, '
                                    + ('SyncBN+RCCL all-reduce' if world > 1 else 'BN, single GPU'),
                        'global_batch': B * world, 'parallelism': f'dp{world}',
@@ -710,7 +766,7 @@ def main(argv=None):
         }
         if capture_note:
             line['config']['capture_note'] = capture_note
-    if world > 1 and not args.no_sync_ab and os.environ.get('HRF_BENCH_LAUNCHED_BY_BENCH') != '1':
+    if world > 1 and args.full and not args.no_sync_ab and os.environ.get('HRF_BENCH_LAUNCHED_BY_BENCH') != '1':
         # started by an external launcher (the driver's torch.distributed.run): rank 0 runs the schedule A/B itself, as a
         # child job, once every rank is done with the GPU-heavy part (a child process, never an exec)
         import torch.distributed as dist

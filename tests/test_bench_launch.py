@@ -115,7 +115,7 @@ def test_two_ranks_share_one_gpu_gloo():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--backend', 'gloo', '--steps', '2', '--warmup', '1',
-                        '--height', '64', '--width', '96', '--no-roofline', '--sync-ab-timeout', '600'],
+                        '--height', '64', '--width', '96', '--no-roofline', '--sync-ab-timeout', '600', '--full'],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{')]

@@ -13,18 +13,18 @@ cp gpurun_out/prof_$R/${R}_* gpurun_out/prof_$R/bench_under_rocprof.log $O/ 2>/d
 cp gpurun_out/prof_$R/${R}_hbm_traffic.json profiles/ 2>/dev/null
 bash tools/prof_stages_pmc.sh $R > $O/prof_stages.log 2>&1
 cp gpurun_out/pmc_stages_$R/${R}_stage_hbm_traffic.json $O/ 2>/dev/null; cp gpurun_out/pmc_stages_$R/${R}_stage_hbm_traffic.json profiles/ 2>/dev/null
-python bench.py --dump-kernels $O/${R}_kernels_graph_timed.json > $O/${R}_bench_line.json 2> $O/bench.err
-python bench.py --model b_nus_bn --no-cpu-baseline --no-neck --no-eager --steps 20 --warmup 5 --dump-kernels $O/${R}_kernels_b_nus.json > $O/${R}_bench_b_nus.json 2>> $O/bench.err
-python bench.py --model t_stf_bn --no-cpu-baseline --no-neck --no-eager --steps 30 --warmup 5 --dump-kernels $O/${R}_kernels_t_stf.json > $O/${R}_bench_t_stf.json 2>> $O/bench.err
+python bench.py --full --dump-kernels $O/${R}_kernels_graph_timed.json > $O/${R}_bench_line.json 2> $O/bench.err
+python bench.py --full --model b_nus_bn --no-cpu-baseline --no-neck --no-eager --steps 20 --warmup 5 --dump-kernels $O/${R}_kernels_b_nus.json > $O/${R}_bench_b_nus.json 2>> $O/bench.err
+python bench.py --full --model t_stf_bn --no-cpu-baseline --no-neck --no-eager --steps 30 --warmup 5 --dump-kernels $O/${R}_kernels_t_stf.json > $O/${R}_bench_t_stf.json 2>> $O/bench.err
 # the reference's own per-GPU training batch for HRFuser-T (3 images: cascade_rcnn_hrfuser_t_1x_nus_r640_l_r_fusion.py:49)
-python bench.py --batch 3 --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_batch3.json 2>> $O/bench.err
+python bench.py --full --batch 3 --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_batch3.json 2>> $O/bench.err
 # the SyncBN configuration on ONE GPU (forced one-rank group): collective main-lane schedule, one communicator per lane, peer-to-peer exchange
-HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=0 python bench.py --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_rccl.json 2>> $O/bench.err
-HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=0 HRF_SYNC_LANE_COMMS=1 python bench.py --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_rccl_lane_comms.json 2>> $O/bench.err
-HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=1 python bench.py --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_p2p.json 2>> $O/bench.err
-HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=1 python bench.py --model b_nus_bn --no-cpu-baseline --no-neck --no-eager --no-roofline --steps 20 --warmup 5 > $O/${R}_bench_forced_p2p_b_nus.json 2>> $O/bench.err
+HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=0 python bench.py --full --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_rccl.json 2>> $O/bench.err
+HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=0 HRF_SYNC_LANE_COMMS=1 python bench.py --full --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_rccl_lane_comms.json 2>> $O/bench.err
+HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=1 python bench.py --full --no-cpu-baseline --no-neck --no-eager --no-roofline > $O/${R}_bench_forced_p2p.json 2>> $O/bench.err
+HRF_FORCE_COLLECTIVES=1 HRF_SYNC_P2P=1 python bench.py --full --model b_nus_bn --no-cpu-baseline --no-neck --no-eager --no-roofline --steps 20 --warmup 5 > $O/${R}_bench_forced_p2p_b_nus.json 2>> $O/bench.err
 # two ranks sharing this GPU (gloo control plane, IPC inboxes): the launcher, the auto-selected peer-to-peer exchange, the sync_ab arms
-python bench.py --gpus 2 --backend gloo --steps 3 --warmup 1 --height 128 --width 192 --no-roofline --sync-ab-timeout 600 > $O/${R}_bench_two_ranks_one_gpu.json 2>> $O/bench.err
+python bench.py --full --gpus 2 --backend gloo --steps 3 --warmup 1 --height 128 --width 192 --no-roofline --sync-ab-timeout 600 > $O/${R}_bench_two_ranks_one_gpu.json 2>> $O/bench.err
 python bench.py --gpus 2 --steps 2 --warmup 1 > $O/${R}_bench_gpus2_on_one_gpu.txt 2>&1; echo "rc $?" >> $O/${R}_bench_gpus2_on_one_gpu.txt
 python tools/lane_stamps.py > $O/${R}_lane_stamps.txt 2>> $O/bench.err
 bash tools/prof_pmc_sq.sh $R > $O/prof_sq.log 2>&1
