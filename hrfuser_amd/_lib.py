@@ -23,6 +23,7 @@ def _header_int(name, default):
 
 STAT_COPIES = _header_int('HRF_STAT_COPIES', 16)   # replication of cross-block accumulators (see header)
 FIN_MAXC = _header_int('HRF_FIN_MAXC', 576)        # widest BatchNorm the consumer kernels finalise on load
+C3X_MAXC = _header_int('HRF_C3X_MAXC', 256)        # most coefficient channels (fin or arrays) the packed 3x3 engine takes
 
 def struct_from_header(tag, path=HEADER):
     """ctypes mirror of `typedef struct <tag> {...} <tag>_t;` in the public header (the header is the single source of

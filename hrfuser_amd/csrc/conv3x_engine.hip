@@ -36,7 +36,7 @@ constexpr int XW = 16;                    // tile width in pixels
 constexpr int XPP = 68;                   // halo pixel pitch (floats): 64 channels + 4 (granule index of pixel x = 17 x: distinct mod 16)
 constexpr int XRP = 18 * XPP + 56;        // halo row pitch = 1280 floats = 0 mod 64 banks
 constexpr int XNT = 256;                  // threads per block
-constexpr int XFC = 256;                  // channels of an on-load BatchNorm the kernel can finalise
+constexpr int XFC = HRF_C3X_MAXC;         // per-channel coefficients the kernel can stage (finalised on load or copied from arrays)
 
 __device__ float g_zero4x[4] = {0.f, 0.f, 0.f, 0.f};
 

@@ -1074,7 +1074,8 @@ extern "C" int hrf_conv_fwd_packed(const float* x, int sB, int sY, int sX, int s
   if (wp == nullptr || !hrf_conv3x_supported(Cin, Cout, KH, stride, 0)) return HRF_ERR_ARG;
   if (!(sC == 1 && sY == W * sX && sB == H * sY) || tf_mode < 0 || tf_mode > HRF_TF_AFFINE_GELU) return HRF_ERR_ARG;
   if (ln_rowstat != nullptr && (ldY != Cout || yoff != 0)) return HRF_ERR_ARG;
-  if (tf_fin != nullptr && (tf_mode < HRF_TF_AFFINE || tf_fin->C != Cin || Cin > 256 || tf_fin->stats == nullptr)) return HRF_ERR_ARG;
+  if (tf_mode != HRF_TF_NONE && Cin > HRF_C3X_MAXC) return HRF_ERR_ARG;        // scale / shift of Cin channels are staged in sFin, fin or arrays
+  if (tf_fin != nullptr && (tf_mode < HRF_TF_AFFINE || tf_fin->C != Cin || tf_fin->stats == nullptr)) return HRF_ERR_ARG;
   C3xArgs c{};
   c.in = x; c.ldIn = sX; c.t0 = tf_scale; c.t1 = tf_shift; c.tf_mode = tf_mode; c.wp = wp;
   c.Np = (Cout + 63) & ~63; c.Kp = (Cin + 31) & ~31; c.bias = bias;
@@ -1103,7 +1104,8 @@ extern "C" int hrf_conv_bwd_data_packed(const float* dy, int ldD, int doff, cons
   (void)w;
   if (wp == nullptr || !hrf_conv3x_supported(Cin, Cout, KH, stride, 1)) return HRF_ERR_ARG;
   if (!(sC == 1 && sY == W * sX && sB == H * sY)) return HRF_ERR_ARG;
-  if (bfin != nullptr && (cA == nullptr || bfin->C != Cout || Cout > 256 || bfin->gstats == nullptr)) return HRF_ERR_ARG;
+  if (cA != nullptr && Cout > HRF_C3X_MAXC) return HRF_ERR_ARG;                // cA / cB / cC of Cout channels are staged in sFin, bfin or arrays
+  if (bfin != nullptr && (cA == nullptr || bfin->C != Cout || bfin->gstats == nullptr)) return HRF_ERR_ARG;
   C3xArgs c{};
   c.in = dy + doff; c.ldIn = ldD; c.in2 = cA != nullptr ? yraw + doff : nullptr; c.t0 = cA; c.t1 = cB; c.t2 = cC;
   c.wp = wp; c.Np = (Cin + 63) & ~63; c.Kp = (Cout + 31) & ~31;

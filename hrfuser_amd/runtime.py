@@ -1340,9 +1340,14 @@ _S2F_MINPIX = int(os.environ.get('HRF_C3X_S2F_MINPIX', '4096'))   # A/B switch: 
 _IM2COL = os.environ.get('HRF_IM2COL', '1') != '0'      # A/B switch: the stem's first convolution through hrf_im2col3x3
 
 
-def _packed(ctx, weight, direction, strides, B, H, W, Cin):
+def _packed(ctx, weight, direction, strides, B, H, W, Cin, coef_channels=0):
     """The tap-major pack of a front-end 3x3 convolution (csrc/conv3x_engine.hip; Engine.packed) when the activation is
-    dense NHWC - None: the call goes through the OIHW entry point."""
+    dense NHWC - None: the call goes through the OIHW entry point.  coef_channels: channels of the per-channel coefficients
+    the call applies on load (forward: Cin when the source carries a transform; backward: Cout when a BatchNorm follows;
+    0: none) - the packed entry points take at most _lib.C3X_MAXC of them (include/hrfuser_hip.h), wider layers go through
+    hrf_conv_fwd / hrf_conv_bwd_data."""
+    if coef_channels > _lib.C3X_MAXC:
+        return None
     eng = ctx.owner._engine()
     wp = eng.packed(weight, direction) if hasattr(eng, 'packed') else None
     if wp is None or tuple(strides) != (H * W * Cin, W * Cin, Cin, 1):
@@ -1358,7 +1363,8 @@ def _conv_backward(ctx, src, weight, bias, KH, stride, Cout, dy, ldD, doff, yraw
     needs = _needs_grad(src)
     # (stride 2: one block walks the four parity classes of a SOURCE tile - worth it from ~64 tiles: 2 x 16 x 24 source pixels
     # measured 34 vs 26 us on the parity-class blocks of conv3_engine.hip)
-    wpb = _packed(ctx, weight, 1, strides, B, H, W, Cin) if (KH == 3 and (stride == 1 or B * H * W >= 16384)) else None
+    wpb = (_packed(ctx, weight, 1, strides, B, H, W, Cin, Cout if st is not None else 0)
+           if (KH == 3 and (stride == 1 or B * H * W >= 16384)) else None)
 
     def bwd_data(*args):
         if wpb is not None:
@@ -1529,7 +1535,7 @@ def conv_bn(ctx, src, conv, bn, mode):
     nsc = L.hrf_conv_fwd_split_scratch(*strides, B, H, W, Cin, KH, stride, Cout, Cout, 0) if KH == 3 else 0
     wp = None
     if nsc == 0 and KH == 3 and tf != TF_LN and (stride == 1 or (B * Ho * Wo >= _S2F_MINPIX and Cin >= 32)):
-        wp = _packed(ctx, w, 0, strides, B, H, W, Cin)
+        wp = _packed(ctx, w, 0, strides, B, H, W, Cin, Cin if tf != TF_NONE else 0)
     if nsc > 0:
         L.hrf_conv_fwd_split(x, *strides, B, H, W, Cin, w, b, KH, stride, Cout, y, Cout, 0, None, None, 0,
                              tf, sc, sh, rowstat, stats, _src_fin(ctx, src), None, 0.0, _new((nsc,), x.device), s)

@@ -50,6 +50,10 @@
  * BatchNorm-backward coefficients (dy = cA*du + cB*y + cC) from `gstats` = replicated (sum du, sum du*y); `write` != 0:
  * block 0 stores cA/cB/cC (read by the weight-gradient kernel) and adds dgamma / dbeta. */
 #define HRF_FIN_MAXC 576
+/* The packed-weight 3x3 engine (csrc/conv3x_engine.hip) stages per-channel coefficients - finalised on load OR handed in as
+ * arrays - in a smaller LDS array: hrf_conv_fwd_packed / hrf_conv_bwd_data_packed take a transform on load (tf_mode != 0) /
+ * a BatchNorm backward on load (cA != NULL) only up to this many coefficient channels (Cin forward, Cout backward). */
+#define HRF_C3X_MAXC 256
 typedef struct hrf_bn_fin {
   const double* stats;
   const float* gamma; const float* beta; float* running_mean; float* running_var;
@@ -130,11 +134,18 @@ int hrf_conv_bwd_weight(const float* dy, int ldD, int doff, const float* yraw,
  *                         dir 0 (forward operand, N = Cout, K = Cin):        wp[tap][n][k] = w[n][k][tap]
  *                         dir 1 (backward-data operand, N = Cin, K = Cout):  wp[tap][n][k] = w[k][n][tap]
  *                         `jobs` is a HOST array; the packs are caller-owned scratch, refreshed whenever w changes (once per step);
- *   hrf_conv3x_supported  1 when hrf_conv_fwd_packed (dir 0) / hrf_conv_bwd_data_packed (dir 1) take the shape:
- *                         KH = 3, NHWC rows; dir 0: stride 1, Cout > 32; dir 1: stride 1, Cin > 32, or stride 2, Cin > 32 and
- *                         Cout <= 64; on-load BatchNorm <= 256 channels.
+ *   hrf_conv3x_supported  1 when hrf_conv_fwd_packed (dir 0) / hrf_conv_bwd_data_packed (dir 1) take the SHAPE:
+ *                         KH = 3; dir 0: stride 1 or 2, Cout > 32; dir 1: stride 1, Cin > 32, or stride 2, Cin > 32 and
+ *                         Cout <= 64.  (The shape only: the coefficient bound below depends on the call's other arguments.)
  *   hrf_conv_fwd_packed / hrf_conv_bwd_data_packed: hrf_conv_fwd / hrf_conv_bwd_data (same arguments, same results) with
- *                         `wp` = the pack of `w` in the matching direction; HRF_ERR_ARG for unsupported shapes. */
+ *                         `wp` = the pack of `w` in the matching direction, on dense NHWC rows.  A call is TAKEN when
+ *                         hrf_conv3x_supported says 1 AND its per-channel coefficients fit the kernel's staging array:
+ *                           forward:  tf_mode == HRF_TF_NONE or Cin  <= HRF_C3X_MAXC (tf_fin and tf_scale / tf_shift alike;
+ *                                     HRF_TF_LN is never taken),
+ *                           backward: cA == NULL             or Cout <= HRF_C3X_MAXC (bfin and cA / cB / cC arrays alike).
+ *                         Every other call returns HRF_ERR_ARG before anything is launched - the caller goes through
+ *                         hrf_conv_fwd / hrf_conv_bwd_data, which take any width on the array route and up to HRF_FIN_MAXC
+ *                         channels on the finalise-on-load route. */
 typedef struct hrf_conv3x_pack_job {
   const float* w; float* wp;
   int Cout, Cin, dir;

@@ -21,9 +21,24 @@ def _cfg():
         return json.load(fh)
 
 
-def _pair(dev):
+def _widen(cfg, C):
+    """the coarsest branch (1/32 resolution) of the last stage at C channels instead of 144: every entry that names it.  Its
+    BASIC blocks then hold 3x3 convolutions with a C-channel BatchNorm + ReLU on load in front and a C-channel BatchNorm
+    behind - past HRF_C3X_MAXC = 256, where the packed 3x3 engine must hand over to hrf_conv_fwd / hrf_conv_bwd_data
+    (stock HRNet widths: w40 ends at 320 channels, w48 at 384)"""
+    ex = cfg['extra']
+    assert ex['stage4']['num_channels'][3] == ex['ModFusionC']['num_channels'][3] == 144
+    ex['stage4']['num_channels'][3] = C
+    ex['ModFusionC']['num_channels'][3] = C
+    assert C % 32 == 0
+    ex['ModFusionC']['num_heads'][3] = C // 32       # 32-channel heads: a width the window-attention kernels are built for (144 / 8 = 18 is another)
+
+
+def _pair(dev, wide=None):
     from hrfuser_amd import build_backbone
     meta = _cfg()
+    if wide is not None:
+        _widen(meta['cfg'], wide)
     kw = copy.deepcopy(meta['cfg'])
     kw.pop('type')
     orc = O.HRFuserHRNetOracle(**kw)
@@ -54,9 +69,9 @@ def test_oracle_matches_reference_golden_and_manifest():
         orc.load_state_dict(sd0)
 
 
-def _run(train, backend):
+def _run(train, backend, wide=None):
     dev = use_backend(backend)
-    net, orc, meta = _pair(dev)
+    net, orc, meta = _pair(dev, wide)
     net.train(train)
     orc.train(train)
     B, H, W = (2, 64, 96) if backend == 'hip' else ((2, 64, 64) if train else (1, 32, 32))   # train: >= 8 samples per BatchNorm
@@ -64,7 +79,7 @@ def _run(train, backend):
     xa = x.clone().to(dev).requires_grad_(True)
     enable_relu_probe(net)
     ya = net(xa, [m.to(dev) for m in mods])
-    if backend == 'hip':
+    if backend == 'hip' and wide is None:         # (the fixture is the reference's output at the golden config)
         gold = np.load(os.path.join(GOLD, 'hrfuser_hrnet.npz'))
         for i, y in enumerate(ya):
             assert relmax(y, torch.as_tensor(gold[f'B2_64x96/{"train" if train else "eval"}/out{i}'])) < 1e-3
@@ -85,7 +100,8 @@ def _run(train, backend):
     sum((t * c.to(dev)).sum() for t, c in zip(ya, cots)).backward()
     e, e_ref = rel_l2(xa.grad, xb.grad), rel_l2(refs[1][2].grad, xb.grad)
     assert e <= max(1e-3, 3 * e_ref), (e, e_ref)
-    tight_grad_gate(net.named_parameters(), o64.named_parameters(), refs[1][0].named_parameters(), 1e-3, f'hrnet-based train={train}')
+    tight_grad_gate(net.named_parameters(), o64.named_parameters(), refs[1][0].named_parameters(), 1e-3,
+                    f'hrnet-based train={train}' + (f' wide={wide}' if wide else ''))
 
 
 @pytest.mark.parametrize('train', [False, True])
@@ -97,3 +113,16 @@ def test_hrnet_based_emul(train):
 @pytest.mark.parametrize('train', [False, True])
 def test_hrnet_based_gpu(train):
     _run(train, 'hip')
+
+
+@pytest.mark.parametrize('train', [False, True])
+@pytest.mark.parametrize('wide', [288])              # (a minute and a half per leg on the emulator; 384 runs on the GPU)
+def test_hrnet_based_wide_emul(wide, train):
+    _run(train, 'emul', wide)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('train', [False, True])
+@pytest.mark.parametrize('wide', [288, 384])
+def test_hrnet_based_wide_gpu(wide, train):
+    _run(train, 'hip', wide)

@@ -135,56 +135,86 @@ def _pack3x(L, w, dev, direction):
     return wp
 
 
-def run_conv(case, backend, packed=False):
+def refused(call, out):
+    """a call its entry point must refuse: HRF_ERR_ARG, and nothing was launched - the output, pre-filled with NaN, is untouched"""
+    out.fill_(float('nan'))
+    with pytest.raises(_lib.HRFuserHipError, match='HRF_ERR_ARG'):
+        call()
+    if out.is_cuda:
+        torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all()), 'a refused call has written to its output'
+
+
+def run_conv(case, backend, packed=False, coef='fin', ref64=None, wgrad=True):
     """packed: forward / backward-data through hrf_conv_fwd_packed / hrf_conv_bwd_data_packed (csrc/conv3x_engine.hip) where
-    hrf_conv3x_supported takes the shape - same arguments, same expected results"""
+    hrf_conv3x_supported takes the shape - same arguments, same expected results.
+    coef: the route of the per-channel coefficients of a BatchNorm applied on load (tf 1..3) - 'fin': finalised in the kernel
+    prologue from replicated moments (hrf_bn_fin_t, train mode); 'array': tf_scale / tf_shift handed in as plain arrays, no fin
+    (eval mode, frozen BatchNorm, every layer wider than the entry point's fin bound).  The backward always runs both of its
+    routes (cA / cB / cC arrays, then hrf_bn_bfin_t).  A route the entry point does not take at this width - fin / bfin past
+    HRF_FIN_MAXC, any coefficients past HRF_C3X_MAXC on the packed entry points - must be REFUSED (see refused()).
+    ref64: the reference in float64 (default: with coef='array'); wgrad=False leaves the weight-gradient legs out (width-envelope
+    cases: those kernels stage coefficients per channel block, not per layer)."""
     dev = use_backend(backend)
     L = _lib.lib()
     B, H, W, Cin, Cout, KH, stride, tf, bnb, epi = case
+    assert coef in ('fin', 'array')
+    assert epi or tf in (0, 1, 4), 'without the act\' epilogue the data gradient is compared with d/du: identity activations only'
+    dt = torch.float64 if (coef == 'array' if ref64 is None else ref64) else torch.float32
+    X = lambda t: t.to(dt)
     conv_fwd, conv_bwd_data = L.hrf_conv_fwd, L.hrf_conv_bwd_data
     if packed:
         assert L.hrf_conv3x_supported(Cin, Cout, KH, stride, 0) or L.hrf_conv3x_supported(Cin, Cout, KH, stride, 1), case
+    fwd_packed = bool(packed and L.hrf_conv3x_supported(Cin, Cout, KH, stride, 0))
+    bwd_packed = bool(packed and L.hrf_conv3x_supported(Cin, Cout, KH, stride, 1))
     g = torch.Generator().manual_seed(sum(case[:7]))
     rn = lambda *s: torch.randn(*s, generator=g)
     xraw, w, bias = rn(B, Cin, H, W), rn(Cout, Cin, KH, KH) * 0.2, rn(Cout)
     fin = ft = None
     sc, sh = torch.rand(Cin, generator=g) + 0.5, rn(Cin) * 0.3
-    if tf in (1, 2, 3):
+    if tf in (1, 2, 3) and coef == 'fin':
         # the input's BatchNorm is finalised ON LOAD from replicated moments (hrf_bn_fin_t): scale / shift are what
         # hrf_bn_finalize derives from the same moments; the kernel gets no scale/shift arrays at all
         fin, ft = make_fin(L, Cin, 977.0, dev, g)
         sc, sh = ft['ref_scale'].cpu(), ft['ref_shift'].cpu()
-    u, xt, rowstat = _tf_apply(xraw, tf, sc, sh)
-    wq, bq = w.clone().requires_grad_(True), bias.clone().requires_grad_(True)
+    u, xt, rowstat = _tf_apply(X(xraw), tf, X(sc), X(sh))
+    wq, bq = X(w).clone().requires_grad_(True), X(bias).clone().requires_grad_(True)
     y = F.conv2d(xt, wq, bq, stride, KH // 2)
     Ho, Wo = y.shape[2:]
     res = rn(B, Ho, Wo, Cout)
-    yref = nhwc(y.detach()) + res
-    D = lambda t: None if t is None else t.to(dev)
+    yref = nhwc(y.detach()) + X(res)
+    D = lambda t: None if t is None else t.float().to(dev)
     xr = nhwc(xraw)
     st = (H * W * Cin, W * Cin, Cin, 1)
     yk = torch.zeros(B, Ho, Wo, Cout, device=dev)
     stats = zstat(Cout, dev)
     lnrs = torch.zeros(B * Ho * Wo, 2, device=dev)      # fused LayerNorm row statistics of the output
-    if packed and L.hrf_conv3x_supported(Cin, Cout, KH, stride, 0):
+    if fwd_packed:
         wpf = _pack3x(L, D(w), dev, 0)
         conv_fwd = lambda *a: L.hrf_conv_fwd_packed(*a[:-1], wpf, a[-1])
-    if packed and L.hrf_conv3x_supported(Cin, Cout, KH, stride, 1):
+    if bwd_packed:
         wpb = _pack3x(L, D(w), dev, 1)
         conv_bwd_data = lambda *a: L.hrf_conv_bwd_data_packed(*a[:-1], wpb, a[-1])
-    conv_fwd(D(xr), *st, B, H, W, Cin, D(w), D(bias), KH, stride, Cout, yk, Cout, 0, D(res), None, Cout,
-             tf, D(sc) if (tf and fin is None) else None, D(sh) if (tf and fin is None) else None, D(rowstat), stats,
-             fin, lnrs, 1e-6, _lib.stream_ptr())
-    if fin is not None:
-        check_fin(ft)
-    yr_ = yref.reshape(-1, Cout)
-    assert r(lnrs[:, 0], yr_.mean(-1)) < TOL and r(lnrs[:, 1], (yr_.var(-1, unbiased=False) + 1e-6).rsqrt()) < 1e-4
-    assert r(yk, yref) < TOL
+    # the contract of include/hrfuser_hip.h: the packed forward stages Cin coefficients of ANY route in HRF_C3X_MAXC slots; every
+    # forward finalises on load up to HRF_FIN_MAXC channels and takes arrays of any width
+    fwd_ok = not ((fwd_packed and tf and Cin > _lib.C3X_MAXC) or (fin is not None and Cin > _lib.FIN_MAXC))
+    fwd_call = lambda: conv_fwd(D(xr), *st, B, H, W, Cin, D(w), D(bias), KH, stride, Cout, yk, Cout, 0, D(res), None, Cout,
+                                tf, D(sc) if (tf and fin is None) else None, D(sh) if (tf and fin is None) else None, D(rowstat),
+                                stats, fin, lnrs, 1e-6, _lib.stream_ptr())
     s1, s2 = yref.reshape(-1, Cout).double().sum(0), (yref.reshape(-1, Cout).double() ** 2).sum(0)
-    assert r(fold(stats)[:Cout], s1) < TOL and r(fold(stats)[Cout:], s2) < TOL
+    if fwd_ok:
+        fwd_call()
+        if fin is not None:
+            check_fin(ft)
+        yr_ = yref.reshape(-1, Cout)
+        assert r(lnrs[:, 0], yr_.mean(-1)) < TOL and r(lnrs[:, 1], (yr_.var(-1, unbiased=False) + 1e-6).rsqrt()) < 1e-4
+        assert r(yk, yref) < TOL
+        assert r(fold(stats)[:Cout], s1) < TOL and r(fold(stats)[Cout:], s2) < TOL
+    else:
+        refused(fwd_call, yk)
     # the split over K (deep 3x3 contractions with few row blocks): same output, same moments, bit-reproducible
     nsc = L.hrf_conv_fwd_split_scratch(*st, B, H, W, Cin, KH, stride, Cout, Cout, 0)
-    if nsc > 0 and not packed:
+    if nsc > 0 and not packed and fwd_ok:
         assert KH == 3 and 9 * Cin >= 1024
         outs = []
         for _ in range(2):
@@ -206,38 +236,62 @@ def run_conv(case, backend, packed=False):
     # ---- backward
     du, yraw = rn(B, Ho, Wo, Cout), rn(B, Ho, Wo, Cout)
     cA, cB, cC = rn(Cout), rn(Cout) * 0.3, rn(Cout) * 0.1
-    dyeff = cA * du + cB * yraw + cC if bnb else du
-    y.backward(dyeff.permute(0, 3, 1, 2))
+    dyeff = X(cA) * X(du) + X(cB) * X(yraw) + X(cC) if bnb else X(du)
+    y.backward(dyeff.permute(0, 3, 1, 2), retain_graph=True)
     gu = nhwc(u.grad)
     co = (D(cA), D(cB), D(cC)) if bnb else (None, None, None)
     act = {0: 0, 1: 0, 2: 1, 3: 2, 4: 0}[tf]
     dx = torch.zeros(B, H, W, Cin, device=dev)
+    # (the packed backward stages Cout coefficients of either route in HRF_C3X_MAXC slots; hrf_bn_bfin_t: up to HRF_FIN_MAXC)
+    bwd_ok = not (bwd_packed and bnb and Cout > _lib.C3X_MAXC)
     if epi:
         gst = zstat(Cin, dev)
-        conv_bwd_data(D(du), Cout, 0, D(yraw), *co, None, D(w), KH, stride, Cout, B, H, W, Cin, dx, *st, 0, 1,
-                            D(xr), Cin, D(sc), D(sh), act, gst, _lib.stream_ptr())
-        assert r(dx, gu) < TOL
-        assert r(fold(gst)[:Cin], gu.reshape(-1, Cin).double().sum(0)) < TOL
-        assert r(fold(gst)[Cin:], (gu.reshape(-1, Cin).double() * xr.reshape(-1, Cin).double()).sum(0)) < TOL
+        bwd_call = lambda: conv_bwd_data(D(du), Cout, 0, D(yraw), *co, None, D(w), KH, stride, Cout, B, H, W, Cin, dx, *st, 0, 1,
+                                         D(xr), Cin, D(sc), D(sh), act, gst, _lib.stream_ptr())
+        if bwd_ok:
+            bwd_call()
+            assert r(dx, gu) < TOL
+            assert r(fold(gst)[:Cin], gu.reshape(-1, Cin).double().sum(0)) < TOL
+            assert r(fold(gst)[Cin:], (gu.reshape(-1, Cin).double() * xr.reshape(-1, Cin).double()).sum(0)) < TOL
+        else:
+            refused(bwd_call, dx)
     else:
         base = rn(B, H, W, Cin)
         dx.copy_(base)
-        conv_bwd_data(D(du), Cout, 0, D(yraw), *co, None, D(w), KH, stride, Cout, B, H, W, Cin, dx, *st, 1, 0,
-                            None, 0, None, None, 0, None, _lib.stream_ptr())
-        assert r(dx, gu + base) < TOL
+        bwd_call = lambda: conv_bwd_data(D(du), Cout, 0, D(yraw), *co, None, D(w), KH, stride, Cout, B, H, W, Cin, dx, *st, 1, 0,
+                                         None, 0, None, None, 0, None, _lib.stream_ptr())
+        if bwd_ok:
+            bwd_call()
+            assert r(dx, gu + X(base)) < TOL
+        else:
+            refused(bwd_call, dx)
     if bnb:
         # BatchNorm-backward coefficients derived ON LOAD (hrf_bn_bfin_t): same data gradient as with the coefficients
         # hrf_bn_bwd_finalize computes from the same moments; block 0 publishes cA/cB/cC and adds dgamma / dbeta
         bfin, bt = make_bfin(L, Cout, 811.0, dev, g)
         dxa, dxb = torch.zeros(B, H, W, Cin, device=dev), torch.zeros(B, H, W, Cin, device=dev)
         tail = (1, D(xr), Cin, D(sc), D(sh), act, zstat(Cin, dev)) if epi else (0, None, 0, None, None, 0, None)
-        conv_bwd_data(D(du), Cout, 0, D(yraw), bt['ref_cA'], bt['ref_cB'], bt['ref_cC'], None, D(w), KH, stride, Cout,
-                            B, H, W, Cin, dxa, *st, 0, *tail, _lib.stream_ptr())
-        tail = (1, D(xr), Cin, D(sc), D(sh), act, zstat(Cin, dev)) if epi else (0, None, 0, None, None, 0, None)
-        conv_bwd_data(D(du), Cout, 0, D(yraw), bt['cA'], bt['cB'], bt['cC'], bfin, D(w), KH, stride, Cout,
-                            B, H, W, Cin, dxb, *st, 0, *tail, _lib.stream_ptr())
-        check_bfin(bt)
-        assert r(dxb, dxa) < 1e-6
+        arr_call = lambda: conv_bwd_data(D(du), Cout, 0, D(yraw), bt['ref_cA'], bt['ref_cB'], bt['ref_cC'], None, D(w), KH, stride,
+                                         Cout, B, H, W, Cin, dxa, *st, 0, *tail, _lib.stream_ptr())
+        tail2 = (1, D(xr), Cin, D(sc), D(sh), act, zstat(Cin, dev)) if epi else (0, None, 0, None, None, 0, None)
+        bfin_call = lambda: conv_bwd_data(D(du), Cout, 0, D(yraw), bt['cA'], bt['cB'], bt['cC'], bfin, D(w), KH, stride, Cout,
+                                          B, H, W, Cin, dxb, *st, 0, *tail2, _lib.stream_ptr())
+        if not bwd_ok:
+            refused(arr_call, dxa)
+            refused(bfin_call, dxb)
+        elif Cout > _lib.FIN_MAXC:               # arrays of any width, the on-load finalize up to HRF_FIN_MAXC channels
+            arr_call()
+            rc = X(bt['ref_cA'].cpu()) * X(du) + X(bt['ref_cB'].cpu()) * X(yraw) + X(bt['ref_cC'].cpu())
+            gref, = torch.autograd.grad(y, u, rc.permute(0, 3, 1, 2))
+            assert r(dxa, nhwc(gref)) < TOL
+            refused(bfin_call, dxb)
+        else:
+            arr_call()
+            bfin_call()
+            check_bfin(bt)
+            assert r(dxb, dxa) < 1e-6
+    if not wgrad:
+        return
     dw, db = torch.zeros_like(w, device=dev), torch.zeros(Cout, device=dev)
     L.hrf_conv_bwd_weight(D(du), Cout, 0, D(yraw), *co, D(xr), *st, B, H, W, Cin, KH, stride, Cout, tf,
                           D(sc) if tf else None, D(sh) if tf else None, D(rowstat), dw, db, _lib.stream_ptr())
@@ -276,13 +330,13 @@ LIN2_CASES = [  # B,H,W,Cin,Cout,KH,stride,tf,bnb,epi
 ]
 
 
-def run_lin2(case, wn, backend):
+def run_lin2(case, wn, backend, **kw):
     use_backend(backend)
     L = _lib.lib()
     L.hrf_debug_knob(28, 1)
     L.hrf_debug_knob(29, wn)
     try:
-        run_conv(case, backend)
+        run_conv(case, backend, **kw)
     finally:
         L.hrf_debug_knob(28, 0)
         L.hrf_debug_knob(29, 0)
@@ -309,23 +363,27 @@ DW_CASES = [(2, 9, 11, 72, 1, 3, True, True, True), (2, 17, 35, 40, 1, 0, False,
             (1, 9, 33, 52, 1, 2, False, True, True)]       # 52 channels = one 13-lane slab of the float4-lane forward (HRFuser-B widths are 13 x 4 x k)
 
 
-def run_dw(case, backend):
+def run_dw(case, backend, coef='fin', ref64=None):
+    """coef / ref64: as in run_conv (the depthwise kernels stage coefficients per 32-channel block: no width bound on either route)"""
     dev = use_backend(backend)
     L = _lib.lib()
     B, H, W, C, S, tf, has_bias, bnb, epi = case
+    assert coef in ('fin', 'array')
+    dt = torch.float64 if (coef == 'array' if ref64 is None else ref64) else torch.float32
+    X = lambda t: t.to(dt)
     g = torch.Generator().manual_seed(sum(case[:5]))
     rn = lambda *s: torch.randn(*s, generator=g)
-    D = lambda t: None if t is None else t.to(dev)
+    D = lambda t: None if t is None else t.float().to(dev)
     xraw, w = rn(B, C, H, W), rn(C, 1, 3, 3) * 0.3
     b = rn(C) if has_bias else None
     sc, sh = torch.rand(C, generator=g) + 0.5, rn(C) * 0.3
     fin = ft = None
-    if tf in (1, 2, 3):                      # input BatchNorm finalised on load, as in run_conv
+    if tf in (1, 2, 3) and coef == 'fin':    # input BatchNorm finalised on load, as in run_conv
         fin, ft = make_fin(L, C, 977.0, dev, g)
         sc, sh = ft['ref_scale'].cpu(), ft['ref_shift'].cpu()
-    u, xt, _ = _tf_apply(xraw, tf, sc, sh)
-    wq, bq = w.clone().requires_grad_(True), torch.zeros(C, requires_grad=True)
-    y = F.conv2d(xt, wq, (b + bq) if has_bias else bq, S, 1, groups=C)
+    u, xt, _ = _tf_apply(X(xraw), tf, X(sc), X(sh))
+    wq, bq = X(w).clone().requires_grad_(True), torch.zeros(C, dtype=dt, requires_grad=True)
+    y = F.conv2d(xt, wq, (X(b) + bq) if has_bias else bq, S, 1, groups=C)
     Ho, Wo = y.shape[2:]
     yk = torch.zeros(B, Ho, Wo, C, device=dev)
     st = zstat(C, dev)
@@ -339,7 +397,7 @@ def run_dw(case, backend):
     assert r(fold(st)[:C], yr.reshape(-1, C).double().sum(0)) < TOL and r(fold(st)[C:], (yr.reshape(-1, C).double() ** 2).sum(0)) < TOL
     du, yraw = rn(B, Ho, Wo, C), rn(B, Ho, Wo, C)
     cA, cB, cC = rn(C), rn(C) * 0.3, rn(C) * 0.1
-    y.backward((cA * du + cB * yraw + cC if bnb else du).permute(0, 3, 1, 2))
+    y.backward((X(cA) * X(du) + X(cB) * X(yraw) + X(cC) if bnb else X(du)).permute(0, 3, 1, 2))
     gu = nhwc(u.grad)
     co = (D(cA), D(cB), D(cC)) if bnb else (None, None, None)
     act = {0: 0, 1: 0, 2: 1, 3: 2}[tf]
@@ -355,7 +413,7 @@ def run_dw(case, backend):
         dx.copy_(base)
         L.hrf_dwconv_bwd_data(D(du), D(yraw), *co, None, D(w), S, B, H, W, C, dx, 1, 0, None, None, None, 0, None,
                               _lib.stream_ptr())
-        assert r(dx, gu + base) < TOL
+        assert r(dx, gu + X(base)) < TOL
     if bnb:                                  # coefficients derived on load (hrf_bn_bfin_t), as in run_conv
         bfin, bt = make_bfin(L, C, 811.0, dev, g)
         dxa, dxb = torch.zeros(B, H, W, C, device=dev), torch.zeros(B, H, W, C, device=dev)
@@ -847,18 +905,26 @@ def test_dwconv_emul(case):
     run_dw(case, 'emul')
 
 
+def run_dw_lane4(mode, backend, cases, **kw):
+    use_backend(backend)
+    L = _lib.lib()
+    L.hrf_debug_knob(40, mode)
+    try:
+        for case in cases:
+            run_dw(case, backend, **kw)
+    finally:
+        L.hrf_debug_knob(40, 1)
+
+
+LANE4_EMUL = [(2, 9, 11, 72, 1, 3, True, True, True), (1, 9, 33, 52, 1, 2, False, True, True)]   # ([1]: one 13-lane slab, ReLU on load)
+LANE4_GPU = [(2, 19, 37, 72, 1, 3, True, True, True), (1, 13, 18, 144, 1, 3, True, True, True)]
+
+
 @pytest.mark.parametrize('mode', [0, 2, 3])
 def test_dwconv_lane4_modes_emul(mode):
     """hrf_debug_knob(40): the float4-lane depthwise forward (not the default: csrc/dwconv.hip) with automatic / 8-row / 4-row
     tiles - same results as the one-channel-lane kernel the other tests run"""
-    use_backend('emul')
-    L = _lib.lib()
-    L.hrf_debug_knob(40, mode)
-    try:
-        run_dw((2, 9, 11, 72, 1, 3, True, True, True), 'emul')
-        run_dw((1, 9, 33, 52, 1, 2, False, True, True), 'emul')          # one 13-lane slab, ReLU on load
-    finally:
-        L.hrf_debug_knob(40, 1)
+    run_dw_lane4(mode, 'emul', LANE4_EMUL)
 
 
 @pytest.mark.parametrize('case', ATTN_CASES[:5], ids=str)
@@ -954,14 +1020,7 @@ def test_dwconv_gpu(case):
 @pytest.mark.gpu
 @pytest.mark.parametrize('mode', [0, 2, 3])
 def test_dwconv_lane4_modes_gpu(mode):
-    use_backend('hip')
-    L = _lib.lib()
-    L.hrf_debug_knob(40, mode)
-    try:
-        run_dw((2, 19, 37, 72, 1, 3, True, True, True), 'hip')
-        run_dw((1, 13, 18, 144, 1, 3, True, True, True), 'hip')
-    finally:
-        L.hrf_debug_knob(40, 1)
+    run_dw_lane4(mode, 'hip', LANE4_GPU)
 
 
 @pytest.mark.gpu
@@ -973,3 +1032,91 @@ def test_attention_gpu(case):
 @pytest.mark.gpu
 def test_pointwise_gpu():
     run_pointwise('hip')
+
+
+# ------------------------------------------------------------------ coefficient route 'array' (eval mode / frozen BatchNorm)
+# The cases above hand every BatchNorm-on-load (tf 1..3) to the kernel as an hrf_bn_fin_t.  Eval mode, norm_eval, and every layer
+# wider than the fin bound pass tf_scale / tf_shift ARRAYS instead: the same cases on that route, one per forward engine, against
+# the float64 reference at the same TOL (the engines sit at 1-2e-6 against float64 on these contractions).
+ARRAY_CONV_CASES = [
+    CONV_CASES[1],                                   # 1x1 row GEMM (lin_engine.hip), GELU on load, act' epilogue
+    CONV_CASES[6],                                   # 1x1, AFFINE, many rows
+    CONV_CASES[16],                                  # 1x1, 288-deep contraction
+    CONV_CASES[2],                                   # 3x3 stride 1: halo engine (conv3_engine.hip), ReLU on load
+    CONV_CASES[4],                                   # 3x3 stride 2: conv_fwd_kernel
+    (1, 9, 11, 128, 36, 3, 2, 3, True, True),        # 3x3 stride 2, 1 152-deep, one row block: conv_fwd_kernel + the split over K with a transform
+]
+ARRAY_CONV_CASES_GPU = ARRAY_CONV_CASES + [CONV_CASES[7], CONV_CASES[10], CONV_CASES[11], CONV_CASES[13], CONV_CASES[14], CONV_CASES[15],
+                                           (1, 33, 47, 256, 36, 3, 2, 2, True, True)]       # ([12] with ReLU on load: the product's split-K shape)
+ARRAY_LIN2_CASES = [c for c in LIN2_CASES if c[7] in (1, 2, 3)]
+ARRAY_C3X_CASES = [c for c in C3X_CASES if c[7] != 0]
+ARRAY_DW_CASES = [c for c in DW_CASES if c[5] != 0]
+
+
+def test_array_case_lists_reach_their_engines():
+    """the selections above are by index / filter: pin what they must contain"""
+    assert all(c[7] in (1, 2, 3) for c in ARRAY_CONV_CASES + ARRAY_CONV_CASES_GPU + ARRAY_LIN2_CASES + ARRAY_C3X_CASES)
+    assert {(c[5], c[6]) for c in ARRAY_CONV_CASES} == {(1, 1), (3, 1), (3, 2)}
+    assert len(ARRAY_C3X_CASES) == 6 and len(ARRAY_LIN2_CASES) == 4 and len(ARRAY_DW_CASES) == 6
+    assert (1, 13, 18, 144, 1, 3, True, True, True) in ARRAY_DW_CASES          # the five-block depthwise case
+    use_backend('emul')
+    L = _lib.lib()
+    B, H, W, Cin, Cout, KH, stride = ARRAY_CONV_CASES[-1][:7]
+    assert L.hrf_conv_fwd_split_scratch(H * W * Cin, W * Cin, Cin, 1, B, H, W, Cin, KH, stride, Cout, Cout, 0) > 0
+
+
+@pytest.mark.parametrize('case', ARRAY_CONV_CASES, ids=str)
+def test_conv_array_emul(case):
+    run_conv(case, 'emul', coef='array')
+
+
+@pytest.mark.parametrize('wn', [1, 3])
+@pytest.mark.parametrize('case', ARRAY_LIN2_CASES, ids=str)
+def test_lin2_array_emul(case, wn):
+    run_lin2(case, wn, 'emul', coef='array')
+
+
+@pytest.mark.parametrize('case', ARRAY_C3X_CASES, ids=str)
+def test_conv3x_array_emul(case):
+    run_conv(case, 'emul', packed=True, coef='array')
+
+
+@pytest.mark.parametrize('case', ARRAY_DW_CASES, ids=str)
+def test_dwconv_array_emul(case):
+    run_dw(case, 'emul', coef='array')
+
+
+@pytest.mark.parametrize('mode', [0, 2, 3])
+def test_dwconv_lane4_modes_array_emul(mode):
+    run_dw_lane4(mode, 'emul', LANE4_EMUL, coef='array')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', ARRAY_CONV_CASES_GPU, ids=str)
+def test_conv_array_gpu(case):
+    run_conv(case, 'hip', coef='array')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('wn', [0, 1, 3])
+@pytest.mark.parametrize('case', ARRAY_LIN2_CASES + [(2, 96, 160, 312, 78, 1, 1, 3, True, True), (2, 96, 160, 64, 256, 1, 1, 2, True, True)], ids=str)
+def test_lin2_array_gpu(case, wn):
+    run_lin2(case, wn, 'hip', coef='array')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', ARRAY_C3X_CASES + [(2, 50, 130, 64, 64, 3, 1, 2, True, True), (2, 37, 70, 64, 64, 3, 2, 2, True, True)], ids=str)
+def test_conv3x_array_gpu(case):
+    run_conv(case, 'hip', packed=True, coef='array')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('case', ARRAY_DW_CASES, ids=str)
+def test_dwconv_array_gpu(case):
+    run_dw(case, 'hip', coef='array')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('mode', [0, 2, 3])
+def test_dwconv_lane4_modes_array_gpu(mode):
+    run_dw_lane4(mode, 'hip', LANE4_GPU, coef='array')
