@@ -72,6 +72,16 @@ def _rel_index():
 
 
 # ----------------------------------------------------------------------------- engine
+def _det_release(L, g_ptr, g_n, ps_ptr, ps_n):
+    """unregister the shadow bins of an engine's accumulators (Engine.det_sync)"""
+    try:
+        L.hrf_det_register(g_ptr, g_n, None)
+        if ps_n:
+            L.hrf_det_register(ps_ptr, ps_n, None)
+    except Exception:                                      # interpreter shutdown: the library may be gone
+        pass
+
+
 class Engine:
     """Device-side state owned by a root module: flat parameter / gradient arenas, per-BatchNorm
     scratch slots, eval-mode BN affine cache, SyncBN group."""
@@ -84,6 +94,10 @@ class Engine:
         self._bns = []
         self.keep = []                 # step-lifetime buffers of THIS engine (runtime.use_keep_list)
         self.fs_layers, self.fs_step, self.fs_used, self.fs_sig, self.fs_arena = {}, [], [], None, None
+        # deterministic mode: (arena the bins belong to, arena bins, replicated-accumulator bins, release) once allocated;
+        # det_epoch counts the mode switches seen through this engine's owner (Trainer.replay compares it);
+        # det_dirty: a backward pass has started adding into the bins and has not resolved them yet
+        self._det_bins, self.det_epoch, self.det_dirty = None, 0, False
 
     def ready(self, device):
         params = [p for p in self.root.parameters()]
@@ -98,6 +112,50 @@ class Engine:
                 dirty = True
         if dirty:
             self.flat_g.zero_()
+        self.det_sync()
+
+    # ---- deterministic mode (include/hrfuser_hip.h: hrf_set_deterministic): the kernels that add into the gradient arena or
+    # into copy 0 of the replicated accumulators with atomics add into SHADOW BINS instead (32 bytes per element, registered
+    # with the library); fold_grads turns the bins into the floats before anything reads them
+    def det_sync(self):
+        """Allocate and register the shadow bins of this engine's accumulators the first time the mode is on."""
+        if self.flat_g is None:
+            return
+        L = self.root._lib_handle()
+        on = bool(L.hrf_get_deterministic())
+        cur = self._det_bins
+        if on and (cur is None or cur[0] is not self.flat_g):
+            if cur is not None:
+                cur[3]()
+            bg = torch.zeros(4 * self.flat_g.numel(), device=self.device, dtype=torch.int64)
+            bs = torch.zeros(4 * max(1, self.ps_n), device=self.device, dtype=torch.int64)
+            L.hrf_det_register(self.flat_g, self.flat_g.numel(), bg)
+            if self.ps_n:
+                L.hrf_det_register(self.ps_scratch, self.ps_n, bs)
+            # the library keeps raw pointers: forget the ranges when this engine goes away
+            import weakref
+            rel = weakref.finalize(self, _det_release, L, self.flat_g.data_ptr(), self.flat_g.numel(),
+                                   self.ps_scratch.data_ptr() if self.ps_n else 0, self.ps_n)
+            self._det_bins = (self.flat_g, bg, bs, rel)
+        # (mode off: the bins stay - a graph captured in deterministic mode carries their addresses; they go with the engine)
+
+    def det_begin(self):
+        """Start of a backward pass in deterministic mode.  The bins are zero whenever the pass before this one got as far as
+        fold_grads (hrf_det_resolve returns them to zero: no memset per step); one that did not - an exception between a
+        producer and the fold - left residue that would be added to THIS step's gradients: zero the bins then."""
+        if self._det_bins is not None:
+            if self.det_dirty:
+                self._det_bins[1].zero_()
+                self._det_bins[2].zero_()
+            self.det_dirty = True
+
+    def det_resolve(self, L, stream):
+        """Shadow bins -> floats (and the bins back to zero); a no-op outside the deterministic mode."""
+        if self._det_bins is not None and L.hrf_get_deterministic():
+            L.hrf_det_resolve(self.flat_g, self.flat_g.numel(), stream)
+            if self.ps_n:
+                L.hrf_det_resolve(self.ps_scratch, self.ps_n, stream)
+            self.det_dirty = False
 
     def _setup(self, device, params):
         total = sum(p.numel() for p in params)
@@ -265,6 +323,7 @@ class Engine:
     def fold_grads(self, L, stream):
         """Sum the replicated accumulators and the per-window slots of the fused attention blocks into the gradient
         arena (one launch each per backward)."""
+        self.det_resolve(L, stream)
         if self.ps_dirty and self.ps_n:
             L.hrf_fold_copies(self.ps_scratch, self.ps_n, self.ps_map, self.flat_g, self.ps_n, stream)
             R.gpu_zero_(self.ps_scratch)
@@ -532,6 +591,25 @@ class EngineOwner:
         self.sync_group, self.sync_world = group, world
         if group is not None:
             R.check_sync_schedule(group, world)
+
+    def set_deterministic(self, on=True):
+        """Deterministic mode of the library (process-wide; include/hrfuser_hip.h: hrf_set_deterministic): every result of a
+        step becomes a bit-exact function of parameters, buffers, inputs and pinned random draws.  Captured module graphs
+        are dropped - a graph replays the mode it was captured in.  What the mode cannot honour raises HRFuserHipError.
+        The mode belongs to the process, the bookkeeping to the net that was called: only THIS net drops its module graphs and
+        counts the switch.  Another net in the process is still safe - the mode is part of every module-graph key (a graph of
+        the other mode is never replayed), a backward pass refuses to run in another mode than its forward, and a net whose
+        engine has no shadow bins yet allocates them at its next forward (Engine.ready) - but its captured Trainer graph
+        only notices a switch that flipped the mode (Trainer.replay compares the mode as well as this count)."""
+        L = self._lib_handle()
+        if bool(L.hrf_get_deterministic()) != bool(on):
+            # the two modes lay out the engine's step tables differently (slot segments, the dS planes): a Trainer graph
+            # captured before the switch holds pointers into tables the next step replaces - Trainer.replay checks this count
+            self._engine().det_epoch += 1
+        L.hrf_set_deterministic(1 if on else 0)
+        self._engine().det_sync()
+        if hasattr(self, 'reset_graphs'):
+            self.reset_graphs()
 
     def params_updated(self):
         """Kept for callers that signal a weight update; nothing is cached across steps any more."""
@@ -1273,7 +1351,7 @@ class HipModule(nn.Module, EngineOwner):
     def _graph_key(self, inputs, record):
         flags = tuple(m.training for m in self._engine()._bns) if self._engine()._bns else ()
         return (self.training, record, tuple((tuple(t.shape), tuple(t.stride()), bool(t.requires_grad)) for t in inputs),
-                hash(flags), R.force_collectives(), self.sync_group is not None)
+                hash(flags), R.force_collectives(), self.sync_group is not None, int(self._lib_handle().hrf_get_deterministic()))
 
     def _graph_entry(self, inputs, record):
         """-> the _GraphEntry to run this call through, or None for an eager call."""

@@ -391,8 +391,8 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(HrfGroup<AttnArgs> g
         }
       }
       if (anypad) {
-        hrf_atomic_add(&a.dkpad[cp + h * D + d], pk);
-        hrf_atomic_add(&a.dvpad[cp + h * D + d], pv);
+        hrf_grad_add(a.dkpad, cp, h * D + d, pk);
+        hrf_grad_add(a.dvpad, cp, h * D + d, pv);
       }
     }
   }
@@ -416,7 +416,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(HrfGroup<AttnArgs> g
     __syncthreads();
     if (threadIdx.x < 169) {
       const int e = threadIdx.x;
-      hrf_atomic_add(&a.drpb[cp + e * a.heads + h], (sBin[e] + sBin[176 + e]) + (sBin[352 + e] + sBin[528 + e]));
+      hrf_grad_add(a.drpb, cp, e * a.heads + h, (sBin[e] + sBin[176 + e]) + (sBin[352 + e] + sBin[528 + e]));
     }
   }
 }
@@ -470,6 +470,9 @@ extern "C" int hrf_window_attn_bwd(const float* q, int ldq, int qoff, const floa
   a.kpad = kpad; a.vpad = vpad; a.rpb = rpb; a.B = B; a.H = H; a.W = W; a.heads = heads;
   a.scale = 1.0f / sqrtf((float)D);
   a.dout = dout; a.lddo = lddo; a.dq = dq; a.lddq = lddq; a.dqoff = dqoff; a.dk = dk; a.lddk = lddk; a.dkoff = dkoff;
+  bool det_ok = true;                                      // deterministic mode: the shadow bins of copy 0 of the three accumulators
+  dkpad = hrf_det_grad(dkpad, det_ok); dvpad = hrf_det_grad(dvpad, det_ok); drpb = hrf_det_grad(drpb, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   a.dv = dv; a.lddv = lddv; a.dvoff = dvoff; a.dkpad = dkpad; a.dvpad = dvpad; a.drpb = drpb; a.copy_stride = copy_stride;
   window_geom(a);
   const int nwin = B * a.nWh * a.nWw;

@@ -513,12 +513,11 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
   }
   if (a.stats1 != nullptr) {
     __syncthreads();
-    double* st = a.stats1 + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * N1;
     for (int e = tid; e < 2 * N1; e += 256) {
       const int which = e / N1, ch = e - which * N1;
       const float s = (sStat[(0 * 2 + which) * N1 + ch] + sStat[(1 * 2 + which) * N1 + ch]) +
                       (sStat[(2 * 2 + which) * N1 + ch] + sStat[(3 * 2 + which) * N1 + ch]);
-      hrf_atomic_add(&st[which * N1 + ch], (double)s);
+      hrf_stat_add(a.stats1, 2 * N1, which * N1 + ch, (double)s);
     }
   }
 }
@@ -1469,9 +1468,8 @@ __global__ __launch_bounds__(64 * (4 + NWB), (NWB == 0 ? (C <= 18 ? 3 : 1) : (C 
   __syncthreads();
   AB_T(9);
   if (tail) {
-    double* st = a.tail_gstats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C;
     for (int e = tid; e < 2 * C; e += NT)
-      hrf_atomic_add(&st[e], (double)((sTst[0][e] + sTst[1][e]) + (sTst[2][e] + sTst[3][e])));
+      hrf_stat_add(a.tail_gstats, 2 * C, e, (double)((sTst[0][e] + sTst[1][e]) + (sTst[2][e] + sTst[3][e])));
   }
   // LayerNorm parameter gradients: sum of the four role-A waves' partials
   for (int e = tid; e < 3 * 2 * C; e += NT) {
@@ -1545,7 +1543,7 @@ __device__ __forceinline__ void rpb_grad_body(const float* ds, int nwin, int hea
         for (int xj = x0; xj <= x1; ++xj) acc += sP[(yj * 7 + xj) * NTOK + (yj + dy) * 7 + xj + dx];
     __syncthreads();
   }
-  if (e < 169) hrf_atomic_add(&drpb[(long)(blockIdx.x % HRF_STAT_COPIES) * copy_stride + e * heads + h], acc);
+  if (e < 169) hrf_grad_add(drpb, (long)(blockIdx.x % HRF_STAT_COPIES) * copy_stride, e * heads + h, acc);
 }
 
 __global__ __launch_bounds__(256) void rpb_grad_kernel(const float* ds, int nwin, int heads, float* drpb, long copy_stride) {
@@ -1606,8 +1604,10 @@ extern "C" int hrf_attn_block_bwd(const hrf_attn_block_t* p, void* stream) {
   if (a.w1 != nullptr && a.bfin1 != nullptr) {
     bf = *a.bfin1;
     if (bf.C != 4 * a.C || bf.gstats == nullptr) return HRF_ERR_ARG;
+    if (!hrf_det_fin_ok(&bf)) return HRF_ERR_ARG;
   }
   a.bfin1 = nullptr;
+  a.tail_gstats = hrf_det_tag(a.tail_gstats);
   ab_geometry(a);
   const int nwin = a.B * a.nWh * a.nWw;
   if (nwin <= 0) return HRF_OK;
@@ -1618,6 +1618,9 @@ extern "C" int hrf_attn_block_bwd(const hrf_attn_block_t* p, void* stream) {
 
 extern "C" int hrf_rpb_grad(const float* ds_plane, int nwin, int heads, float* drpb, long copy_stride, void* stream) {
   if (nwin <= 0 || heads <= 0) return HRF_OK;
+  bool det_ok = true;                                      // deterministic mode: the shadow bins of copy 0 of drpb
+  drpb = hrf_det_grad(drpb, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   const int chunks = nwin < HRF_RPB_CHUNKS ? nwin : HRF_RPB_CHUNKS;
   HRF_LAUNCH(rpb_grad_kernel, dim3(chunks, heads), dim3(256), 0, stream, ds_plane, nwin, heads, drpb, copy_stride);
   return hrf_check_launch();
@@ -1626,6 +1629,9 @@ extern "C" int hrf_rpb_grad(const float* ds_plane, int nwin, int heads, float* d
 extern "C" int hrf_rpb_grad_all(const float* planes, const long* seg, int nseg, int max_nwin, int max_heads, void* stream) {
   if (nseg <= 0 || max_nwin <= 0 || max_heads <= 0) return HRF_OK;
   if (planes == nullptr || seg == nullptr || nseg > 65535 || max_heads > 65535) return HRF_ERR_ARG;
+  // the accumulator addresses sit in a DEVICE table: the host cannot map them to their shadow bins - deterministic mode takes
+  // hrf_rpb_grad per layer
+  if (hrf_det_on()) return HRF_ERR_ARG;
   const int chunks = max_nwin < HRF_RPB_CHUNKS ? max_nwin : HRF_RPB_CHUNKS;
   HRF_LAUNCH(rpb_grad_all_kernel, dim3(chunks, max_heads, nseg), dim3(256), 0, stream, planes, seg);
   return hrf_check_launch();
@@ -1651,9 +1657,11 @@ extern "C" int hrf_attn_block_fwd(const hrf_attn_block_t* p, void* stream) {
     if (a.tail_fin != nullptr) {
       fin = *a.tail_fin;
       if (fin.C != a.C || fin.stats == nullptr) return HRF_ERR_ARG;
+      if (!hrf_det_fin_ok(&fin)) return HRF_ERR_ARG;
     } else if (a.tail_scale == nullptr || a.tail_shift == nullptr) return HRF_ERR_ARG;
   }
   a.tail_fin = nullptr;
+  a.stats1 = hrf_det_tag(a.stats1);
   ab_geometry(a);
   const int nwin = a.B * a.nWh * a.nWw;
   if (nwin <= 0) return HRF_OK;

@@ -214,7 +214,6 @@ __global__ __launch_bounds__(64 * NWV) void conv3_kernel(HrfGroup<Conv3Args> grp
       if (lane < 16) { sStat[(wave * 2 + 0) * (NT * 16) + tt * 16 + lane] = u1; sStat[(wave * 2 + 1) * (NT * 16) + tt * 16 + lane] = u2; }
     }
     __syncthreads();
-    double* st = a.stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.Cout;
     for (int e = tid; e < 2 * NT * 16; e += 64 * NWV) {
       const int which = e / (NT * 16), cidx = e - which * (NT * 16);
       const int ch = n0 + cidx;
@@ -222,7 +221,7 @@ __global__ __launch_bounds__(64 * NWV) void conv3_kernel(HrfGroup<Conv3Args> grp
         float sm = 0.f;
 #pragma unroll
         for (int wv = 0; wv < NWV; ++wv) sm += sStat[(wv * 2 + which) * (NT * 16) + cidx];
-        hrf_atomic_add(&st[which * a.Cout + ch], (double)sm);
+        hrf_stat_add(a.stats, 2 * a.Cout, which * a.Cout + ch, (double)sm);
       }
     }
   }

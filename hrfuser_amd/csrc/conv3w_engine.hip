@@ -628,6 +628,7 @@ extern "C" long hrf_conv3_wgrad_wide_scratch(int B, int H, int W, int Cin, int C
 extern "C" int hrf_conv3_wgrad_wide(const float* dy, int ldD, const float* x, int ldX, int B, int H, int W, int Cin,
                                     int Cout, float* dw, float* dbias, float* scratch, void* stream) {
   if (Cin <= 0 || Cout <= 0 || Cin % GN != 0 || Cout % GM != 0 || scratch == nullptr) return HRF_ERR_ARG;
+  if (dbias != nullptr && hrf_det_on()) return HRF_ERR_ARG;   // deterministic mode: the bias gradient is an fp32 atomic - refused (header)
   if (B <= 0 || H <= 0 || W <= 0) return HRF_OK;
   W3wArgs a{dy, ldD, x, ldX, scratch, dbias, B, H, W, Cin, Cout, hrf_cdiv(W, GW), hrf_cdiv(H, GH), 0, 0, Cin / GN};
   a.tiles = a.tilesX * a.tilesY * B;

@@ -405,8 +405,7 @@ __global__ __launch_bounds__(XNT, 2) void conv3x_kernel(HrfGroup<C3xArgs> grp) {
         float sm = 0.f;
 #pragma unroll
         for (int w = 0; w < RP; ++w) sm += sStat[(w * 2 + which) * NB + cidx];
-        double* st = a.stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.Cout;
-        hrf_atomic_add(&st[which * a.Cout + c], (double)sm);
+        hrf_stat_add(a.stats, 2 * a.Cout, which * a.Cout + c, (double)sm);
       }
     }
     s1 = 0.f; s2 = 0.f;

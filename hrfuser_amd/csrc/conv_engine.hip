@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void conv_fwd_kernel(HrfGroup<ConvFwdArgs> grp
       const int c = tid < BN ? tid : tid - BN;
       if (n0 + c < a.Cout) {
         const float s = sStat[tid] + sStat[2 * BN + tid] + sStat[4 * BN + tid] + sStat[6 * BN + tid];
-        hrf_atomic_add(&a.stats[(size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.Cout + (tid < BN ? 0 : a.Cout) + n0 + c], (double)s);
+        hrf_stat_add(a.stats, 2 * a.Cout, (tid < BN ? 0 : a.Cout) + n0 + c, (double)s);
       }
     }
   }
@@ -385,7 +385,7 @@ __global__ __launch_bounds__(256) void conv_bwd_data_kernel(HrfGroup<ConvBwdData
       const int c = tid < BN ? tid : tid - BN;
       if (n0 + c < a.Cin) {
         const float s = sStat[tid] + sStat[2 * BN + tid] + sStat[4 * BN + tid] + sStat[6 * BN + tid];
-        hrf_atomic_add(&a.stats[(size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.Cin + (tid < BN ? 0 : a.Cin) + n0 + c], (double)s);
+        hrf_stat_add(a.stats, 2 * a.Cin, (tid < BN ? 0 : a.Cin) + n0 + c, (double)s);
       }
     }
   }
@@ -535,7 +535,7 @@ __global__ __launch_bounds__(256) void conv_bwd_wgt_kernel(ConvBwdWgtArgs a) {
         const int cco = m0 + ti[q] * 16 + (lane >> 4) * 4 + r;
         if (cco < a.Cout && nn < a.Np) {
           const int o = a.KH == 3 ? (cco * a.Cin + c9) * 9 + t9 : cco * a.Cin + nn;
-          if (a.dbg_plain) a.dw[o] = acc[q][r]; else hrf_atomic_add(&a.dw[o], acc[q][r]);
+          if (a.dbg_plain) a.dw[o] = acc[q][r]; else hrf_grad_add(a.dw, 0, o, acc[q][r]);
         }
       }
     }
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(256) void conv_bwd_wgt_kernel(ConvBwdWgtArgs a) {
   sBias[wave * 64 + lane] = bias_part;
   __syncthreads();
   if (a.dbias != nullptr && blockIdx.y == 0 && tid < 64 && m0 + tid < a.Cout)
-    hrf_atomic_add(&a.dbias[m0 + tid], sBias[tid] + sBias[64 + tid] + sBias[128 + tid] + sBias[192 + tid]);
+    hrf_grad_add(a.dbias, 0, m0 + tid, sBias[tid] + sBias[64 + tid] + sBias[128 + tid] + sBias[192 + tid]);
 }
 
 // ----------------------------------------------------------- backward weight, dense 1x1 (no LDS staging)
@@ -791,7 +791,7 @@ __global__ __launch_bounds__(64 * WNW) void wgrad_dense_kernel(WgradGroup grp_ar
       const int w = ((ti * NT + tap) * 64 + (rr >> 2) * 16 + cil) * 4 + (rr & 3);
       float v = sAcc[w];
       if (NREG == 2) v += sAcc[MT * NT * 256 + w];
-      if (m0 + row < a.Cout && n0 + cil < a.Cin) hrf_atomic_add(&a.dw[(long)(m0 + row) * Np + (n0 + cil) * 9 + tap], v);
+      if (m0 + row < a.Cout && n0 + cil < a.Cin) hrf_grad_add(a.dw, 0, (long)(m0 + row) * Np + (n0 + cil) * 9 + tap, v);
     }
   } else {
     const hrf_f4* S0 = reinterpret_cast<const hrf_f4*>(sAcc);
@@ -804,7 +804,7 @@ __global__ __launch_bounds__(64 * WNW) void wgrad_dense_kernel(WgradGroup grp_ar
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = m0 + 16 * ti + 4 * (l >> 4) + r;
-        if (row < a.Cout && col < Np) hrf_atomic_add(&a.dw[(long)row * Np + col], v0[r]);
+        if (row < a.Cout && col < Np) hrf_grad_add(a.dw, 0, (long)row * Np + col, v0[r]);
       }
     }
   }
@@ -815,7 +815,7 @@ __global__ __launch_bounds__(64 * WNW) void wgrad_dense_kernel(WgradGroup grp_ar
     float t = 0.f;
 #pragma unroll
     for (int w = 0; w < WNW; ++w) t += sBias[w * (MT * 16) + tid];
-    hrf_atomic_add(&a.dbias[m0 + tid], t);
+    hrf_grad_add(a.dbias, 0, m0 + tid, t);
   }
 }
 
@@ -843,7 +843,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(float* y, const floa
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
     double t = 0.0;
     for (int rr = 0; rr < R; ++rr) t += (double)sacc[(size_t)rr * 2 * C + i];
-    hrf_atomic_add(&stats[(size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C + i], t);
+    hrf_stat_add(stats, 2 * C, i, t);
   }
 }
 
@@ -905,7 +905,9 @@ static int conv_fwd_impl(const float* x, int sB, int sY, int sX, int sC, int B, 
   a.x = x; a.w = w; a.bias = bias; a.y = y; a.ldY = ldY; a.yoff = yoff; a.res = res; a.res2 = res2; a.ldR = ldR;
   a.tf_scale = tf_scale; a.tf_shift = tf_shift; a.tf_rowstat = tf_rowstat;
   a.fin = hrf_bn_fin_t{};
+  if (!hrf_det_fin_ok(tf_fin)) return HRF_ERR_ARG;
   if (tf_fin != nullptr) a.fin = *tf_fin;
+  stats = hrf_det_tag(stats);
   a.stats = stats; a.B = B; a.H = H; a.W = W; a.Cin = Cin;
   a.Ho = (H + 2 * pad - KH) / stride + 1; a.Wo = (W + 2 * pad - KH) / stride + 1;
   a.Cout = Cout; a.stride = stride; a.pad = pad; a.sB = sB; a.sY = sY; a.sX = sX; a.sC = sC;
@@ -1010,7 +1012,9 @@ extern "C" int hrf_conv_bwd_data(const float* dy, int ldD, int doff, const float
   ConvBwdDataArgs a;
   const int pad = KH / 2;
   a.bfin = hrf_bn_bfin_t{};
+  if (!hrf_det_fin_ok(bfin)) return HRF_ERR_ARG;
   if (bfin != nullptr) a.bfin = *bfin;
+  stats = hrf_det_tag(stats);
   a.dy = dy; a.ldD = ldD; a.doff = doff; a.yraw = yraw; a.cA = cA; a.cB = cB; a.cC = cC; a.w = w;
   a.dx = dx; a.sB = sB; a.sY = sY; a.sX = sX; a.sC = sC; a.accumulate = accumulate; a.epi = epi;
   a.xraw = xraw; a.ldXr = ldXr; a.tf_scale = tf_scale; a.tf_shift = tf_shift; a.act = act; a.stats = stats;
@@ -1079,8 +1083,9 @@ extern "C" int hrf_conv_fwd_packed(const float* x, int sB, int sY, int sX, int s
   C3xArgs c{};
   c.in = x; c.ldIn = sX; c.t0 = tf_scale; c.t1 = tf_shift; c.tf_mode = tf_mode; c.wp = wp;
   c.Np = (Cout + 63) & ~63; c.Kp = (Cin + 31) & ~31; c.bias = bias;
-  c.out = y; c.ldOut = ldY; c.ooff = yoff; c.res = res; c.res2 = res2; c.ldR = ldR; c.stats = stats;
+  c.out = y; c.ldOut = ldY; c.ooff = yoff; c.res = res; c.res2 = res2; c.ldR = ldR; c.stats = hrf_det_tag(stats);
   c.B = B; c.H = H; c.W = W; c.Cin = Cin; c.Cout = Cout;
+  if (!hrf_det_fin_ok(tf_fin)) return HRF_ERR_ARG;
   if (tf_fin != nullptr) c.fin = *tf_fin;
   int rc;
   if (stride == 2) {                                             // the source grid is the input, tiles walk the output grid
@@ -1110,7 +1115,8 @@ extern "C" int hrf_conv_bwd_data_packed(const float* dy, int ldD, int doff, cons
   c.in = dy + doff; c.ldIn = ldD; c.in2 = cA != nullptr ? yraw + doff : nullptr; c.t0 = cA; c.t1 = cB; c.t2 = cC;
   c.wp = wp; c.Np = (Cin + 63) & ~63; c.Kp = (Cout + 31) & ~31;
   c.out = dx; c.ldOut = sX; c.accumulate = accumulate; c.epi = epi; c.xraw = xraw; c.ldXr = ldXr;
-  c.esc = tf_scale; c.esh = tf_shift; c.act = act; c.stats = stats;
+  c.esc = tf_scale; c.esh = tf_shift; c.act = act; c.stats = hrf_det_tag(stats);
+  if (!hrf_det_fin_ok(bfin)) return HRF_ERR_ARG;
   if (bfin != nullptr) c.bfin = *bfin;
   c.B = B; c.H = H; c.W = W; c.Cin = Cout; c.Cout = Cin;
   if (stride == 1) return hrf_conv3x_bwd_data_launch(c, stream);
@@ -1153,6 +1159,9 @@ extern "C" int hrf_conv_bwd_weight(const float* dy, int ldD, int doff, const flo
                                    int tf_mode, const float* tf_scale, const float* tf_shift,
                                    const float* tf_rowstat, float* dw, float* dbias, void* stream) {
   if ((KH != 1 && KH != 3) || (stride != 1 && stride != 2)) return HRF_ERR_ARG;
+  bool det_ok = true;                                      // deterministic mode: the kernels add into the shadow bins of dw / dbias
+  dw = hrf_det_grad(dw, det_ok); dbias = hrf_det_grad(dbias, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   ConvBwdWgtArgs a;
   const int pad = KH / 2;
   a.dy = dy; a.ldD = ldD; a.doff = doff; a.yraw = yraw; a.cA = cA; a.cB = cB; a.cC = cC;
@@ -1170,7 +1179,7 @@ extern "C" int hrf_conv_bwd_weight(const float* dy, int ldD, int doff, const flo
   int cap = hrf_cdiv(512, gx * gy);
   if (cap > 64) cap = 64;                                  // atomic fan-in per output element
   if (g_knob[0] > 0) cap = g_knob[0];
-  a.dbg_plain = g_knob[1];
+  a.dbg_plain = hrf_det_on() ? 0 : g_knob[1];
   if (splits > cap) splits = cap;
   if (splits < 1) splits = 1;
   a.chunk = hrf_cdiv(hrf_cdiv(a.Mpix, splits), WK) * WK;

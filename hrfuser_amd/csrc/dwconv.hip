@@ -144,8 +144,7 @@ __global__ __launch_bounds__(256) void dw_fwd_kernel(HrfGroup<DwFwdArgs> grp) {
       float tot = 0.f;
 #pragma unroll
       for (int g = 0; g < 8; ++g) tot += sStat[g * 2 * CB + tid];
-      double* st = a.stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.C;
-      hrf_atomic_add(&st[(tid < CB ? 0 : a.C) + c0 + (tid & (CB - 1))], (double)tot);
+      hrf_stat_add(a.stats, 2 * a.C, (tid < CB ? 0 : a.C) + c0 + (tid & (CB - 1)), (double)tot);
     }
   }
 }
@@ -273,8 +272,7 @@ __global__ __launch_bounds__(16 * D4_MAXL) void dw4_fwd_kernel(HrfGroup<DwFwdArg
       float tot = 0.f;
 #pragma unroll
       for (int q = 0; q < 16; ++q) tot += sRed[(q * 2 + which) * CS + ch];
-      double* st = a.stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.C;
-      hrf_atomic_add(&st[(which ? a.C : 0) + c0 + ch], (double)tot);
+      hrf_stat_add(a.stats, 2 * a.C, (which ? a.C : 0) + c0 + ch, (double)tot);
     }
   }
 }
@@ -290,14 +288,14 @@ __device__ __forceinline__ void dw_wgt_tail(const float* sAcc, float* dw, float*
     float tot = 0.f;
 #pragma unroll
     for (int g = 0; g < 8; ++g) tot += sAcc[(g * 10 + k) * CB + cl];
-    hrf_atomic_add(&dw[cp + (long)c0 * 9 + i], tot);
+    hrf_grad_add(dw, cp, (long)c0 * 9 + i, tot);
   }
   const int cl = tid - (256 - CB);                        // the bias sums: the last CB threads (they sit out the second pass above)
   if (dbias != nullptr && cl >= 0 && cl < nc) {
     float tot = 0.f;
 #pragma unroll
     for (int g = 0; g < 8; ++g) tot += sAcc[(g * 10 + 9) * CB + cl];
-    hrf_atomic_add(&dbias[cp + c0 + cl], tot);
+    hrf_grad_add(dbias, cp, c0 + cl, tot);
   }
 }
 
@@ -452,8 +450,7 @@ __global__ __launch_bounds__(256) void dw_bwd_data_kernel(HrfGroup<DwBwdDataArgs
       float tot = 0.f;
 #pragma unroll
       for (int g = 0; g < 8; ++g) tot += sStat[g * 2 * CB + tid];
-      double* st = a.stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * a.C;
-      hrf_atomic_add(&st[(tid < CB ? 0 : a.C) + c0 + (tid & (CB - 1))], (double)tot);
+      hrf_stat_add(a.stats, 2 * a.C, (tid < CB ? 0 : a.C) + c0 + (tid & (CB - 1)), (double)tot);
     }
   }
   if (WG) {
@@ -628,8 +625,9 @@ extern "C" int hrf_dwconv_fwd(const float* x, int B, int H, int W, int C, const 
   if (stride != 1 && stride != 2) return HRF_ERR_ARG;
   if (tf_fin != nullptr && (tf_mode < HRF_TF_AFFINE || tf_mode > HRF_TF_AFFINE_GELU || tf_fin->C != C || tf_fin->stats == nullptr)) return HRF_ERR_ARG;
   DwFwdArgs a;
-  a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = stats; a.tf_mode = tf_mode; a.tf_scale = tf_scale;
+  a.x = x; a.w = w; a.bias = bias; a.y = y; a.stats = hrf_det_tag(stats); a.tf_mode = tf_mode; a.tf_scale = tf_scale;
   a.fin = hrf_bn_fin_t{};
+  if (!hrf_det_fin_ok(tf_fin)) return HRF_ERR_ARG;
   if (tf_fin != nullptr) a.fin = *tf_fin;
   a.tf_shift = tf_shift; a.B = B; a.H = H; a.W = W; a.C = C;
   a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
@@ -661,11 +659,15 @@ static int dw_bwd_data_launch(const float* dy, const float* yraw, const float* c
   if (stride != 1 && stride != 2) return HRF_ERR_ARG;
   if (dw != nullptr && (stride != 1 || epi != 1 || xraw == nullptr)) return HRF_ERR_ARG;
   if (bfin != nullptr && (cA == nullptr || bfin->C != C || bfin->gstats == nullptr)) return HRF_ERR_ARG;
+  bool det_ok = true;                                      // deterministic mode: the shadow bins of copy 0 of dw / dbias
+  dw = hrf_det_grad(dw, det_ok); dbias = hrf_det_grad(dbias, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   DwBwdDataArgs a;
   a.bfin = hrf_bn_bfin_t{};
+  if (!hrf_det_fin_ok(bfin)) return HRF_ERR_ARG;
   if (bfin != nullptr) a.bfin = *bfin;
   a.dy = dy; a.yraw = yraw; a.cA = cA; a.cB = cB; a.cC = cC; a.w = w; a.dx = dx; a.accumulate = accumulate;
-  a.epi = epi; a.xraw = xraw; a.tf_scale = tf_scale; a.tf_shift = tf_shift; a.act = act; a.stats = stats;
+  a.epi = epi; a.xraw = xraw; a.tf_scale = tf_scale; a.tf_shift = tf_shift; a.act = act; a.stats = hrf_det_tag(stats);
   a.B = B; a.H = H; a.W = W; a.C = C; a.Ho = (H - 1) / stride + 1; a.Wo = (W - 1) / stride + 1;
   a.tilesX = hrf_cdiv(W, TW); a.tilesY = hrf_cdiv(H, 8);
   if ((long)B * H * W <= 0) return HRF_OK;
@@ -701,6 +703,9 @@ extern "C" int hrf_dwconv_bwd_weight(const float* dy, const float* yraw, const f
                                      int tf_mode, const float* tf_scale, const float* tf_shift, float* dw,
                                      float* dbias, long copy_stride, void* stream) {
   if (stride != 1 && stride != 2) return HRF_ERR_ARG;
+  bool det_ok = true;
+  dw = hrf_det_grad(dw, det_ok); dbias = hrf_det_grad(dbias, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   DwBwdWgtArgs a;
   a.dy = dy; a.yraw = yraw; a.cA = cA; a.cB = cB; a.cC = cC; a.x = x; a.tf_mode = tf_mode;
   a.tf_scale = tf_scale; a.tf_shift = tf_shift; a.dw = dw; a.dbias = dbias; a.copy_stride = copy_stride;

@@ -100,3 +100,86 @@ extern "C" long hrf_group_count(int what) {
   if (what == 3) return HRF_GROUP_MAX;                 // problems per launch this library was compiled for (1: pass-through)
   return (what >= 0 && what < 3) ? g_count[what] : -1;
 }
+
+// ---------------------------------------------------------------------------------------------- deterministic mode
+// (include/hrfuser_hip.h: hrf_set_deterministic).  The mode is process-wide host state that every entry point reads when it
+// ISSUES a launch (hrf_det_tag / hrf_det_grad in hrf_common.h put it into the launch's pointer arguments), so a
+// captured graph replays the mode it was captured in.  Shadow bins of the fp32 gradient accumulators: a small table of
+// registered ranges, looked up on the host per call.
+#include <atomic>
+#include <mutex>
+#include "hrf_common.h"
+
+namespace {
+std::atomic<int> g_det{0};
+struct DetRange { float* base; long n; long long* bins; };
+constexpr int DET_MAX_RANGES = 64;
+DetRange g_det_ranges[DET_MAX_RANGES];
+int g_det_nranges = 0;
+std::mutex g_det_mu;
+
+// the registered range that holds [p, p + n)
+bool det_find(const float* p, long n, DetRange& out) {
+  std::lock_guard<std::mutex> lk(g_det_mu);
+  for (int i = 0; i < g_det_nranges; ++i) {
+    const DetRange& r = g_det_ranges[i];
+    if (p >= r.base && p + n <= r.base + r.n) { out = r; return true; }
+  }
+  return false;
+}
+
+// g[i] += value(bins of i) where any bin is set, and the bins return to zero: ready for the next step without a memset
+__global__ __launch_bounds__(256) void det_resolve_kernel(float* g, long long* bins, long n) {
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    long long* b = bins + HRF_DET_BINS * i;
+    const long long b0 = b[0], b1 = b[1], b2 = b[2], b3 = b[3];
+    if ((b0 | b1 | b2 | b3) != 0) {
+      g[i] += (float)hrf_det_value(b0, b1, b2, b3);
+      b[0] = 0; b[1] = 0; b[2] = 0; b[3] = 0;
+    }
+  }
+}
+}  // namespace
+
+int hrf_det_on() { return g_det.load(std::memory_order_relaxed); }
+
+float* hrf_det_grad(float* g, bool& ok) {
+  if (g == nullptr || !hrf_det_on()) return g;
+  DetRange r;
+  if (!det_find(g, 1, r)) { ok = false; return nullptr; }
+  return reinterpret_cast<float*>(reinterpret_cast<unsigned long long>(r.bins + HRF_DET_BINS * (g - r.base)) | 1ull);
+}
+
+extern "C" int hrf_set_deterministic(int on) {
+  if (on && HRF_STAT_COPIES < HRF_DET_BINS) return HRF_ERR_ARG;   // the moment bins are the copies of a slot
+  g_det.store(on ? 1 : 0, std::memory_order_relaxed);
+  return HRF_OK;
+}
+extern "C" int hrf_get_deterministic(void) { return hrf_det_on(); }
+
+extern "C" long hrf_det_bins_bytes(long n) { return n > 0 ? (long)(HRF_DET_BINS * sizeof(long long)) * n : 0; }
+
+extern "C" int hrf_det_register(float* base, long n, void* bins) {
+  if (base == nullptr || n <= 0 || (reinterpret_cast<unsigned long long>(bins) & 7ull) != 0) return HRF_ERR_ARG;
+  std::lock_guard<std::mutex> lk(g_det_mu);
+  int w = 0;
+  for (int i = 0; i < g_det_nranges; ++i)                         // drop what the new range overlaps (re-allocated arenas)
+    if (!(base + n <= g_det_ranges[i].base || g_det_ranges[i].base + g_det_ranges[i].n <= base)) continue;
+    else g_det_ranges[w++] = g_det_ranges[i];
+  g_det_nranges = w;
+  if (bins == nullptr) return HRF_OK;
+  if (g_det_nranges == DET_MAX_RANGES) return HRF_ERR_ARG;
+  g_det_ranges[g_det_nranges++] = DetRange{base, n, static_cast<long long*>(bins)};
+  return HRF_OK;
+}
+
+extern "C" int hrf_det_resolve(float* g, long n, void* stream) {
+  if (g == nullptr || n < 0) return HRF_ERR_ARG;
+  if (n == 0) return HRF_OK;
+  DetRange r;
+  if (!det_find(g, n, r)) return HRF_ERR_ARG;
+  long nb = (n + 255) / 256;
+  if (nb > 2048) nb = 2048;
+  HRF_LAUNCH(det_resolve_kernel, dim3((unsigned)nb), dim3(256), 0, stream, g, r.bins + HRF_DET_BINS * (g - r.base), n);
+  return hrf_check_launch();
+}

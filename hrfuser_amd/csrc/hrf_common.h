@@ -16,6 +16,48 @@ enum {
 };
 enum { HRF_ACT_NONE = 0, HRF_ACT_RELU = 1, HRF_ACT_GELU = 2 };
 
+// ------------------------------------------------------------------ cross-block accumulation, both modes (hrf_rt.h)
+// stats: a replicated moment slot [HRF_STAT_COPIES][n2] doubles.  Default: a double atomic into the copy of this block.
+// Deterministic (tagged pointer): the four copies of element idx ARE its four integer bins.
+__device__ __forceinline__ void hrf_stat_add(double* stats, int n2, int idx, double v) {
+  if (hrf_det_tagged(stats)) hrf_det_add(reinterpret_cast<long long*>(hrf_det_untag(stats)) + idx, n2, v);
+  else hrf_atomic_add(stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * n2 + idx, v);
+}
+// g: an fp32 gradient accumulator, element cp + idx (cp = the offset of this block's replicated copy, 0 without copies).
+// Deterministic (tagged pointer): g points at the shadow bins of element 0 (hrf_det_register: 4 consecutive words per element)
+// and every block adds into the bins of copy 0; hrf_det_resolve turns them into the float.
+__device__ __forceinline__ void hrf_grad_add(float* g, long cp, long idx, float v) {
+  if (hrf_det_tagged(g)) hrf_det_add(reinterpret_cast<long long*>(hrf_det_untag(g)) + HRF_DET_BINS * idx, 1, (double)v);
+  else hrf_atomic_add(g + cp + idx, v);
+}
+// (sum, second moment) of channel c of a slot, whichever way it was accumulated: the stand-alone finalize kernels and
+// hrf_bn_pack.  (The finalize-on-load prologues of the consumer kernels do NOT take bins: inlined there - or even called out of
+// line - the 64-bit integer chains cost default-mode kernels registers, one its occupancy step and one 48 bytes of scratch;
+// deterministic mode finalises with the separate launches and the entry points refuse a replicated slot on load.)
+__device__ __forceinline__ void hrf_stat_load_any(const double* stats, int C, int c, double& s1, double& s2) {
+  if (hrf_det_tagged(stats)) {
+    const long long* b = reinterpret_cast<const long long*>(hrf_det_untag(stats)) + c;
+    const size_t n2 = 2 * (size_t)C;
+    s1 = hrf_det_value(b[0], b[n2], b[2 * n2], b[3 * n2]);
+    s2 = hrf_det_value(b[C], b[n2 + C], b[2 * n2 + C], b[3 * n2 + C]);
+    return;
+  }
+  s1 = 0.0; s2 = 0.0;
+#pragma unroll
+  for (int k = 0; k < HRF_STAT_COPIES; ++k) { s1 += stats[(size_t)k * 2 * C + c]; s2 += stats[(size_t)k * 2 * C + C + c]; }
+}
+// host side (group.hip): the process-wide mode and what the entry points do with it
+int hrf_det_on();                                             // hrf_get_deterministic()
+inline double* hrf_det_tag(double* p) { return (p != nullptr && hrf_det_on()) ? (double*)((unsigned long long)p | 1ull) : p; }
+inline const double* hrf_det_tag(const double* p) { return hrf_det_tag(const_cast<double*>(p)); }
+// a finalise-on-load descriptor in deterministic mode: only folded moments (copies == 1: hrf_bn_pack's plain doubles) can be
+// finalised on load - a replicated slot holds bins, which the consumer prologues do not read: the entry point refuses
+inline bool hrf_det_fin_ok(const hrf_bn_fin_t* f) { return f == nullptr || f->stats == nullptr || f->copies == 1 || !hrf_det_on(); }
+inline bool hrf_det_fin_ok(const hrf_bn_bfin_t* f) { return f == nullptr || f->gstats == nullptr || f->copies == 1 || !hrf_det_on(); }
+// gradient accumulator -> what the kernel is handed.  Default mode: g itself.  Deterministic: the tagged shadow bins of g
+// (hrf_det_register); `ok` turns false when g is not registered - the entry point returns HRF_ERR_ARG before any launch.
+float* hrf_det_grad(float* g, bool& ok);
+
 // erf(z), branch-free: Abramowitz-Stegun 7.1.26, erf(|z|) = 1 - t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2) with
 // t = 1 / (1 + p |z|); in fp32 |error| <= 6.1e-7 absolute (GELU: 4.7e-7, its derivative 3.3e-7 - the accuracy of the previous
 // two-polynomial fit and closer to the exact value than torch's own fp32 GELU, 1.2e-6).  ~11 VALU operations + one reciprocal

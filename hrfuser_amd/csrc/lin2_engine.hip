@@ -146,14 +146,13 @@ __device__ __forceinline__ void moments_out(float* sRed, double* stats, int N, i
     }
   }
   __syncthreads();
-  double* st = stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * N;
   for (int e = threadIdx.x; e < 2 * CW; e += NTHR) {
     const int which = e / CW, c = e - which * CW;
     if (chbase + c < N) {
       float s = 0.f;
 #pragma unroll
       for (int g = 0; g < T::NRG; ++g) s += sRed[(g * 2 + which) * CW + c];
-      hrf_atomic_add(&st[which * N + chbase + c], (double)s);
+      hrf_stat_add(stats, 2 * N, which * N + chbase + c, (double)s);
     }
   }
 }

@@ -101,14 +101,13 @@ __device__ __forceinline__ void wave_moments(float* sStat, int wave, int j, int 
 
 template <int NT>
 __device__ __forceinline__ void flush_moments(const float* sStat, double* stats, int n0w, int N) {
-  double* st = stats + (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * N;
   for (int i = threadIdx.x; i < 2 * NT * 16; i += 256) {
     const int which = i / (NT * 16), cidx = i - which * (NT * 16);
     const int ch = n0w + cidx;
     if (ch < N) {
       const float s = sStat[(0 * 2 + which) * (NT * 16) + cidx] + sStat[(1 * 2 + which) * (NT * 16) + cidx] +
                       sStat[(2 * 2 + which) * (NT * 16) + cidx] + sStat[(3 * 2 + which) * (NT * 16) + cidx];
-      hrf_atomic_add(&st[which * N + ch], (double)s);
+      hrf_stat_add(stats, 2 * N, which * N + ch, (double)s);
     }
   }
 }

@@ -150,6 +150,7 @@ extern "C" int hrf_p2p_tick(long* gen, void* stream) {
 extern "C" int hrf_p2p_exchange(const hrf_p2p_t* ctx, const double* const* stats, const int* C, int n, const double* rows,
                                 const long* slot_off, const int* slot_id, double* packed, int phase, void* stream) {
   if (n <= 0) return HRF_OK;
+  if (hrf_det_on()) return HRF_ERR_ARG;                    // deterministic mode: the cross-rank exchange is refused (header)
   if (ctx == nullptr || stats == nullptr || C == nullptr || slot_off == nullptr || slot_id == nullptr || packed == nullptr) return HRF_ERR_ARG;
   if (ctx->world < 1 || ctx->world > HRF_P2P_MAX_RANKS || ctx->rank < 0 || ctx->rank >= ctx->world || ctx->gen == nullptr) return HRF_ERR_ARG;
   for (int p = 0; p < ctx->world; ++p) if (ctx->inbox[p] == nullptr || ctx->flags[p] == nullptr) return HRF_ERR_ARG;

@@ -23,9 +23,8 @@ __global__ void bn_finalize_kernel(const double* stats, const float* gamma, cons
                                    float* mean_out, float* invstd_out, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-  for (int k = 0; k < HRF_STAT_COPIES; ++k) { s1 += stats[(size_t)k * 2 * C + c]; s2 += stats[(size_t)k * 2 * C + C + c]; }
+  double s1, s2;
+  hrf_stat_load_any(stats, C, c, s1, s2);
   const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
   float sc, sh, meanf, invstd;
   double var;
@@ -42,13 +41,10 @@ __global__ void bn_bwd_finalize_kernel(const double* gstats, const double* gstat
                                        float* dgamma, float* dbeta, float* cA, float* cB, float* cC, int C) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
-  double sdu = 0.0, sdux = 0.0, ldu = 0.0, ldux = 0.0;
-#pragma unroll
-  for (int k = 0; k < HRF_STAT_COPIES; ++k) {
-    sdu += gstats[(size_t)k * 2 * C + c]; sdux += gstats[(size_t)k * 2 * C + C + c];
-    if (gstats_local) { ldu += gstats_local[(size_t)k * 2 * C + c]; ldux += gstats_local[(size_t)k * 2 * C + C + c]; }
-  }
-  if (!gstats_local) { ldu = sdu; ldux = sdux; }
+  double sdu, sdux, ldu, ldux;
+  hrf_stat_load_any(gstats, C, c, sdu, sdux);
+  if (gstats_local) hrf_stat_load_any(gstats_local, C, c, ldu, ldux);
+  else { ldu = sdu; ldux = sdux; }
   const double mu = mean[c], is = invstd[c], g = gamma ? gamma[c] : 1.f;
   // parameter grads use the rank-LOCAL moments (data-parallel grads are averaged afterwards);
   // the dy coefficients use the (SyncBN: all-reduced) global moments.
@@ -69,8 +65,13 @@ __global__ __launch_bounds__(256) void bn_pack_kernel(BnPackArgs a, double* pack
   if (a.roff[e] >= 0 && blockIdx.x == 0 && threadIdx.x == 0) packed[a.roff[e]] = a.rows[e];   // this rank's sample count
   for (int c = blockIdx.x * 256 + threadIdx.x; c < C2; c += gridDim.x * 256) {
     double s = 0.0;
+    if (hrf_det_tagged(a.src[e])) {                              // deterministic mode: the copies are the bins of the element
+      const long long* b = reinterpret_cast<const long long*>(hrf_det_untag(a.src[e]));
+      s = hrf_det_value(b[c], b[(size_t)C2 + c], b[2 * (size_t)C2 + c], b[3 * (size_t)C2 + c]);
+    } else {
 #pragma unroll
-    for (int k = 0; k < HRF_STAT_COPIES; ++k) s += a.src[e][(size_t)k * C2 + c];
+      for (int k = 0; k < HRF_STAT_COPIES; ++k) s += a.src[e][(size_t)k * C2 + c];
+    }
     packed[a.off[e] + c] = s;
   }
 }
@@ -237,8 +238,8 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(HrfGroup<LnBwdArgs> grp) {
   __syncthreads();
   const long cp = (long)(blockIdx.x % HRF_STAT_COPIES) * copy_stride;
   for (int i = threadIdx.x; i < C; i += 256) {
-    hrf_atomic_add(&dgamma[cp + i], (sacc[i] + sacc[2 * CW + i]) + (sacc[4 * CW + i] + sacc[6 * CW + i]));
-    hrf_atomic_add(&dbeta[cp + i], (sacc[CW + i] + sacc[3 * CW + i]) + (sacc[5 * CW + i] + sacc[7 * CW + i]));
+    hrf_grad_add(dgamma, cp, i, (sacc[i] + sacc[2 * CW + i]) + (sacc[4 * CW + i] + sacc[6 * CW + i]));
+    hrf_grad_add(dbeta, cp, i, (sacc[CW + i] + sacc[3 * CW + i]) + (sacc[5 * CW + i] + sacc[7 * CW + i]));
   }
 }
 
@@ -653,23 +654,41 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(HrfGroup<ActBwdArgs> grp) 
     }
   }
   __syncthreads();
+  if (hrf_det_tagged(st1) || hrf_det_tagged(st2) || hrf_det_tagged(st3)) {
+    // deterministic mode: the R row groups add into LDS one after the other (block-uniform branch and trip count)
+    for (int rr = 0; rr < R; ++rr) {
+      if (r == rr) {
 #pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    if (vj[j]) {
-      const int cj = c + 256 * j;
-      hrf_atomic_add(&sacc[cj], a0[j]);
-      if (st1) hrf_atomic_add(&sacc[C + cj], a1[j]);
-      if (st2) hrf_atomic_add(&sacc[2 * C + cj], a2[j]);
-      if (st3) hrf_atomic_add(&sacc[3 * C + cj], a3[j]);
+        for (int j = 0; j < 3; ++j) {
+          if (vj[j]) {
+            const int cj = c + 256 * j;
+            sacc[cj] += a0[j];
+            if (st1) sacc[C + cj] += a1[j];
+            if (st2) sacc[2 * C + cj] += a2[j];
+            if (st3) sacc[3 * C + cj] += a3[j];
+          }
+        }
+      }
+      __syncthreads();
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      if (vj[j]) {
+        const int cj = c + 256 * j;
+        hrf_atomic_add(&sacc[cj], a0[j]);
+        if (st1) hrf_atomic_add(&sacc[C + cj], a1[j]);
+        if (st2) hrf_atomic_add(&sacc[2 * C + cj], a2[j]);
+        if (st3) hrf_atomic_add(&sacc[3 * C + cj], a3[j]);
+      }
     }
   }
   __syncthreads();
-  const size_t cp = (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C;
   for (int cc = threadIdx.x; cc < C; cc += 256) {
     const double s = (double)sacc[cc];
-    if (st1) { hrf_atomic_add(&st1[cp + cc], s); hrf_atomic_add(&st1[cp + C + cc], (double)sacc[C + cc]); }
-    if (st2) { hrf_atomic_add(&st2[cp + cc], s); hrf_atomic_add(&st2[cp + C + cc], (double)sacc[2 * C + cc]); }
-    if (st3) { hrf_atomic_add(&st3[cp + cc], s); hrf_atomic_add(&st3[cp + C + cc], (double)sacc[3 * C + cc]); }
+    if (st1) { hrf_stat_add(st1, 2 * C, cc, s); hrf_stat_add(st1, 2 * C, C + cc, (double)sacc[C + cc]); }
+    if (st2) { hrf_stat_add(st2, 2 * C, cc, s); hrf_stat_add(st2, 2 * C, C + cc, (double)sacc[2 * C + cc]); }
+    if (st3) { hrf_stat_add(st3, 2 * C, cc, s); hrf_stat_add(st3, 2 * C, C + cc, (double)sacc[3 * C + cc]); }
   }
 }
 
@@ -749,12 +768,11 @@ __global__ __launch_bounds__(256) void act_bwd_vec_kernel(HrfGroup<ActBwdArgs> g
   }
   __syncthreads();
   sacc = stot;
-  const size_t cp = (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C;
   for (int cc = threadIdx.x; cc < C; cc += 256) {
     const double s = (double)sacc[cc];
-    if (st1) { hrf_atomic_add(&st1[cp + cc], s); hrf_atomic_add(&st1[cp + C + cc], (double)sacc[C + cc]); }
-    if (st2) { hrf_atomic_add(&st2[cp + cc], s); hrf_atomic_add(&st2[cp + C + cc], (double)sacc[2 * C + cc]); }
-    if (st3) { hrf_atomic_add(&st3[cp + cc], s); hrf_atomic_add(&st3[cp + C + cc], (double)sacc[3 * C + cc]); }
+    if (st1) { hrf_stat_add(st1, 2 * C, cc, s); hrf_stat_add(st1, 2 * C, C + cc, (double)sacc[C + cc]); }
+    if (st2) { hrf_stat_add(st2, 2 * C, cc, s); hrf_stat_add(st2, 2 * C, C + cc, (double)sacc[2 * C + cc]); }
+    if (st3) { hrf_stat_add(st3, 2 * C, cc, s); hrf_stat_add(st3, 2 * C, C + cc, (double)sacc[3 * C + cc]); }
   }
 }
 
@@ -914,8 +932,7 @@ __global__ __launch_bounds__(256) void nearest_up_bwd_kernel(const float* g, int
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
     float t = 0.f;
     for (int rr = 0; rr < R; ++rr) t += sacc[(size_t)rr * 2 * C + i];
-    const size_t cp = (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C;
-    hrf_atomic_add(&stats[cp + i], (double)t);
+    hrf_stat_add(stats, 2 * C, i, (double)t);
   }
 }
 
@@ -1045,8 +1062,7 @@ __global__ __launch_bounds__(256) void bilinear_up_bwd_kernel(HrfGroup<BilUpBwdA
   for (int i = threadIdx.x; i < 2 * C; i += 256) {
     float t = 0.f;
     for (int rr = 0; rr < R; ++rr) t += sacc[(size_t)rr * 2 * C + i];
-    const size_t cp = (size_t)(blockIdx.x % HRF_STAT_COPIES) * 2 * C;
-    hrf_atomic_add(&stats[cp + i], (double)t);
+    hrf_stat_add(stats, 2 * C, i, (double)t);
   }
 }
 
@@ -1217,7 +1233,7 @@ inline int ew_grid(long total) {
 extern "C" int hrf_bn_finalize(const double* stats, const float* gamma, const float* beta, float* running_mean,
                                float* running_var, double count, float eps, float momentum, int update_running,
                                float* scale, float* shift, float* mean_out, float* invstd_out, int C, void* stream) {
-  HRF_LAUNCH(bn_finalize_kernel, dim3(hrf_cdiv(C, 64)), dim3(64), 0, stream, stats, gamma, beta, running_mean,
+  HRF_LAUNCH(bn_finalize_kernel, dim3(hrf_cdiv(C, 64)), dim3(64), 0, stream, hrf_det_tag(stats), gamma, beta, running_mean,
              running_var, count, eps, momentum, update_running, scale, shift, mean_out, invstd_out, C);
   return hrf_check_launch();
 }
@@ -1226,7 +1242,7 @@ extern "C" int hrf_bn_bwd_finalize(const double* gstats, const double* gstats_lo
                                    const float* mean, const float* invstd,
                                    double count, int train, float* dgamma, float* dbeta, float* cA, float* cB,
                                    float* cC, int C, void* stream) {
-  HRF_LAUNCH(bn_bwd_finalize_kernel, dim3(hrf_cdiv(C, 64)), dim3(64), 0, stream, gstats, gstats_local, gamma, mean, invstd, count,
+  HRF_LAUNCH(bn_bwd_finalize_kernel, dim3(hrf_cdiv(C, 64)), dim3(64), 0, stream, hrf_det_tag(gstats), hrf_det_tag(gstats_local), gamma, mean, invstd, count,
              train, dgamma, dbeta, cA, cB, cC, C);
   return hrf_check_launch();
 }
@@ -1243,6 +1259,9 @@ extern "C" int hrf_ln_bwd(const float* da, const float* x, const float* rowstat,
   HRF_GROUP_CALL();
   if (rows <= 0) return HRF_OK;
   if (C > 640) return HRF_ERR_ARG;
+  bool det_ok = true;                                      // deterministic mode: the shadow bins of copy 0 of dgamma / dbeta
+  dgamma = hrf_det_grad(dgamma, det_ok); dbeta = hrf_det_grad(dbeta, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
   const int lpr = C > 80 ? 64 : 16, nch = hrf_cdiv(C, lpr);
   const int nrb = hrf_cdiv(rows, 256 / lpr);
   // passes per block: ~640 blocks at most - every block ends with 2*C global atomics, and at 1 920 blocks those were the
@@ -1266,6 +1285,7 @@ static long gn_chunk(long rows_per_sample, int B) {
 extern "C" int hrf_gn_moments(const float* v, const float* w, int B, long rows_per_sample, int C, double* out, void* stream) {
   if (B <= 0 || rows_per_sample <= 0 || C <= 0) return HRF_OK;
   if (v == nullptr || out == nullptr || C > 4096) return HRF_ERR_ARG;
+  if (hrf_det_on()) return HRF_ERR_ARG;                    // [B][2][C] fp64 atomics without copies to hold bins: refused (header)
   const long chunk = gn_chunk(rows_per_sample, B);
   HRF_LAUNCH(gn_moments_kernel, dim3(hrf_cdiv(rows_per_sample, chunk), B), dim3(256), (unsigned)(2 * C * sizeof(float)), stream,
              v, w, rows_per_sample, C, out, chunk);
@@ -1301,6 +1321,7 @@ extern "C" int hrf_affine_act_res(const float* y1, const float* sc1, const float
   if (total <= 0) return HRF_OK;
   if ((fin1 != nullptr && (fin1->C != C || C > HRF_FIN_MAXC || fin1->stats == nullptr)) ||
       (fin2 != nullptr && (fin2->C != C || C > HRF_FIN_MAXC || fin2->stats == nullptr || y2 == nullptr))) return HRF_ERR_ARG;
+  if (!hrf_det_fin_ok(fin1) || !hrf_det_fin_ok(fin2)) return HRF_ERR_ARG;
   const hrf_bn_fin_t f1 = fin1 != nullptr ? *fin1 : hrf_bn_fin_t{}, f2 = fin2 != nullptr ? *fin2 : hrf_bn_fin_t{};
   if (ln_rowstat != nullptr && act_first && y2 == nullptr && C <= 640) {
     const int nch = hrf_cdiv(C, 16);
@@ -1335,6 +1356,7 @@ extern "C" int hrf_act_bwd(const float* dout, const float* out, const float* y1,
   HRF_GROUP_CALL();
   if (rows * C <= 0) return HRF_OK;
   if (C > 768) return HRF_ERR_ARG;
+  st1 = hrf_det_tag(st1); st2 = hrf_det_tag(st2); st3 = hrf_det_tag(st3);
   const int passes = g_pw_knob[1] > 0 ? g_pw_knob[1] : 4;                          // passes per block
   const int vw = g_pw_knob[2] == 1 ? 0 : (C % 4 == 0 ? 4 : (C % 2 == 0 ? 2 : 0));   // (hrf_debug_knob 18 = 1: dword kernel)
   if (vw != 0 && C >= 4 * vw && C / vw <= 256) {
@@ -1365,6 +1387,7 @@ extern "C" int hrf_fuse_sum(int type0, const float* p0, const float* sc0, const 
     a.fin[k] = hrf_bn_fin_t{};
     if (fins != nullptr && fins[k].stats != nullptr) {
       if (fins[k].C != C || C > HRF_FIN_MAXC / 2) return HRF_ERR_ARG;
+      if (!hrf_det_fin_ok(&fins[k])) return HRF_ERR_ARG;
       a.fin[k] = fins[k];
     }
   }
@@ -1391,7 +1414,7 @@ extern "C" int hrf_bilinear_up_bwd(const float* g, int ldG, int goff, int B, int
   int grid = hrf_cdiv(npix, R);
   if (grid > 1024) grid = 1024;
   HRF_LAUNCH_G(bilinear_up_bwd_kernel, dim3(grid), dim3(256), (unsigned)((size_t)R * 2 * C * sizeof(float)), stream,
-               (BilUpBwdArgs{g, ldG, goff, B, H, W, C, ylow, Hs, Ws, du, stats}));
+               (BilUpBwdArgs{g, ldG, goff, B, H, W, C, ylow, Hs, Ws, du, hrf_det_tag(stats)}));
   return hrf_check_launch();
 }
 
@@ -1404,7 +1427,7 @@ extern "C" int hrf_nearest_up_bwd(const float* g, int ldG, int goff, int B, int 
   int grid = hrf_cdiv(npix, R);
   if (grid > 1024) grid = 1024;
   HRF_LAUNCH(nearest_up_bwd_kernel, dim3(grid), dim3(256), (size_t)R * 2 * C * sizeof(float), stream, g, ldG, goff,
-             B, H, W, C, ylow, Hs, Ws, du, stats);
+             B, H, W, C, ylow, Hs, Ws, du, hrf_det_tag(stats));
   return hrf_check_launch();
 }
 
@@ -1493,7 +1516,7 @@ extern "C" int hrf_bn_pack(const double* const* stats, const int* C, int n, cons
     const int m = n - b < PK_MAX ? n - b : PK_MAX;
     int cmax = 0;
     for (int k = 0; k < m; ++k) {
-      a.src[k] = stats[b + k]; a.C[k] = C[b + k]; a.off[k] = off; off += 2 * C[b + k]; if (C[b + k] > cmax) cmax = C[b + k];
+      a.src[k] = hrf_det_tag(stats[b + k]); a.C[k] = C[b + k]; a.off[k] = off; off += 2 * C[b + k]; if (C[b + k] > cmax) cmax = C[b + k];
       a.roff[k] = rows != nullptr ? tail + b + k : -1;
       a.rows[k] = rows != nullptr ? rows[b + k] : 0.0;
     }

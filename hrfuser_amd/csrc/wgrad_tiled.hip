@@ -203,7 +203,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_tiled_kernel(WgradGroup grp) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int row = m0 + 16 * t + 4 * kq + r;
-          if (row < a.Cout && col < a.Cin) hrf_atomic_add(&a.dw[(long)row * Np + col], acc[t][r]);
+          if (row < a.Cout && col < a.Cin) hrf_grad_add(a.dw, 0, (long)row * Np + col, acc[t][r]);
         }
     }
     if (a.dbias != nullptr && by == 0 && wave == 0) {
@@ -211,7 +211,7 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_tiled_kernel(WgradGroup grp) {
       for (int t = 0; t < MT; ++t) {
         float b = bs[t];
         b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-        if (kq == 0 && m0 + 16 * t + c < a.Cout) hrf_atomic_add(&a.dbias[m0 + 16 * t + c], b);
+        if (kq == 0 && m0 + 16 * t + c < a.Cout) hrf_grad_add(a.dbias, 0, m0 + 16 * t + c, b);
       }
     }
   } else {
@@ -229,14 +229,14 @@ __global__ __launch_bounds__(NTHR, 2) void wgrad_tiled_kernel(WgradGroup grp) {
         for (int r = 0; r < 4; ++r) {
           const int co = n0 + 16 * wave + 4 * kq + r;
           const float v = sT[c * 17 + 4 * kq + r];
-          if (co < a.Cout && ci < a.Cin) hrf_atomic_add(&a.dw[(long)co * Np + ci], v);
+          if (co < a.Cout && ci < a.Cin) hrf_grad_add(a.dw, 0, (long)co * Np + ci, v);
         }
         HRF_WAVE_SYNC();
       }
       if (a.dbias != nullptr && bx == 0) {
         float b = bq;
         b += __shfl_xor(b, 16); b += __shfl_xor(b, 32);
-        if (kq == 0 && n0 + 16 * wave + c < a.Cout) hrf_atomic_add(&a.dbias[n0 + 16 * wave + c], b);
+        if (kq == 0 && n0 + 16 * wave + c < a.Cout) hrf_grad_add(a.dbias, 0, n0 + 16 * wave + c, b);
       }
     }
   }

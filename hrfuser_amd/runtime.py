@@ -410,6 +410,9 @@ class Ctx:
     def __init__(self, owner, training, record):
         self.lib = owner._lib_handle()
         self.L = _LibProxy(self, self.lib)
+        # deterministic mode (include/hrfuser_hip.h): the replicated moments hold integer bins, which only the stand-alone
+        # finalize launches read - no finalize on load of a replicated slot (the entry points would refuse it)
+        self.det = bool(self.lib.hrf_get_deterministic())
         self.training = training
         self.record = record            # build the backward tape?
         self.owner = owner
@@ -947,6 +950,12 @@ class Ctx:
                 'BatchNorm statistics slots and step buffers of its engine, so `net(x1); net(x2); loss.backward()` would '
                 'back-propagate x1 with the statistics of x2.  Run backward before the next forward of the same module '
                 '(or use two module instances).')
+        if self.det != bool(self.lib.hrf_get_deterministic()):
+            raise _lib.HRFuserHipError('backward of a forward pass that ran in the other deterministic mode: the moment slots '
+                                       'of the forward hold ' + ('integer bins' if self.det else 'doubles') + ' the backward '
+                                       'kernels would misread (set_deterministic between forward and backward)')
+        if self.det:
+            eng.det_begin()
         use_keep_list(self.owner._engine().keep)
         self.owner._engine().fs_prepare()
         # HRF_WGRAD=flush: every time all lanes are joined into the main lane and enough weight gradients are queued,
@@ -1225,7 +1234,7 @@ def bn_forward(ctx, bn, raw, stats):
         st.count = float(rows * ctx.world)
         if _collectives(ctx):
             ctx.sync_wait(st)                           # batched with the exchanges of the sibling lanes (Ctx.parallel)
-        elif _FIN_ONLOAD:
+        elif _FIN_ONLOAD and not ctx.det:
             st.pending = 'fwd'
         else:
             _finalize_now(ctx, st)
@@ -1317,7 +1326,7 @@ def bn_backward_coef(ctx, st, consumer_follows=True, limit=FIN_MAXC):
             return st.coef, bf
         ctx.L.hrf_bn_bwd_finalize_packed(bf, 1, packed.data_ptr() + 8 * off, lptr, ctx.stream)
         return st.coef, None
-    if _FIN_ONLOAD and consumer_follows and not coll and st.C <= limit:
+    if _FIN_ONLOAD and consumer_follows and not coll and st.C <= limit and not ctx.det:
         P = _lib._ptr
         return st.coef, _lib.BnBFin(P(st.gstats), P(st.bn.weight), P(st.mean), P(st.invstd), P(wg), P(bg), P(cA), P(cB),
                                     P(cC), st.count, 1 if st.train else 0, 1, st.C)
@@ -1813,7 +1822,9 @@ def attn_block(ctx, key, heads, xq, xkv, lnq, lnkv, wq, wk, wv, rpb, out_proj, r
     entries += [('gq', lnq.weight, 0, C), ('btq', lnq.bias, 0, C)]
     if cross:
         entries += [('gkv', lnkv.weight, 0, C), ('btkv', lnkv.bias, 0, C)]
-    rpb_one = rpb.requires_grad and os.environ.get('HRF_RPB_ONE', '1') != '0'      # one gather launch per step (0: one per layer)
+    # one gather launch per step (0: one per layer; deterministic mode: per layer - hrf_rpb_grad_all reads its accumulator
+    # addresses from a device table and cannot be pointed at their shadow bins)
+    rpb_one = rpb.requires_grad and os.environ.get('HRF_RPB_ONE', '1') != '0' and not L.hrf_get_deterministic()
     offs = eng.fs_register(key, nwin, entries, rpb if rpb_one else None, heads if rpb_one else 0)
 
     def bwd():

@@ -26,8 +26,10 @@ NO_DECAY_KEYS = ('absolute_pos_embed', 'relative_position_bias_table', 'norm')
 
 class Trainer:
     def __init__(self, net, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, group=None,
-                 world_size=1, n_buckets=4):
+                 world_size=1, n_buckets=4, deterministic=None):
         self.net = net
+        if deterministic is not None:        # None: follow the net (net.set_deterministic / HRF_DETERMINISTIC)
+            net.set_deterministic(bool(deterministic))
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.group, self.world = group, world_size
         self.n_buckets = n_buckets
@@ -36,6 +38,7 @@ class Trainer:
             net.set_sync_group(group, world_size)
         self._ready = False
         self.graph = None
+        self._graph_det = None               # (deterministic mode, engine's det_epoch) the graph was captured in
         self.collectives_per_step = 0
 
     # -------------------------------------------------------------------------------------------
@@ -94,6 +97,10 @@ class Trainer:
         net = self.net
         eng = net._engine()
         L = net._lib_handle()
+        if L.hrf_get_deterministic() and (self.world > 1 or self.force):
+            raise _lib.HRFuserHipError('deterministic mode: a gradient / SyncBN exchange over a process group is not supported '
+                                       '(the cross-rank summation order is outside the mode; a forced one-rank group takes the '
+                                       'same exchange path and is refused with it): Trainer with a process group')
         R.gpu_zero_(eng.flat_g)
         ctx, outs, _ = net._execute((x,) + tuple(mods), True)
         for o, c in zip(outs, cots):
@@ -175,6 +182,7 @@ class Trainer:
         with R.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
             self._graph_outs = self._step_impl(x, mods, cots)
         self.graph = g
+        self._graph_det = (int(self.net._lib_handle().hrf_get_deterministic()), self.net._engine().det_epoch)
         px = self._exchange()
         if px is not None:
             px.pin()                     # the graph's exchange launches carry the context's inbox / flag / counter pointers
@@ -182,6 +190,9 @@ class Trainer:
         return g
 
     def replay(self):
+        if self._graph_det != (int(self.net._lib_handle().hrf_get_deterministic()), self.net._engine().det_epoch):
+            raise _lib.HRFuserHipError('Trainer.replay: the deterministic mode was switched since this graph was captured '
+                                       '(net.set_deterministic) - capture again')
         self.graph.replay()
         self._poll_exchange()
 

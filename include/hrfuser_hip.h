@@ -537,6 +537,43 @@ const char* hrf_build_digest(void);
 /* Measurement and tuning entry points (GPU time stamps inside a captured graph, the critical-lane probe, kernel tuning knobs,
  * the in-situ timing report of the grouped weight gradients) are NOT part of this interface: include/hrfuser_hip_debug.h. */
 
+/* ---- deterministic mode (opt-in, off by default; csrc/hrf_rt.h has the arithmetic) ---------------------------------------
+ * hrf_set_deterministic(1): every later call of this library accumulates its cross-block sums - the replicated BatchNorm
+ * moments and the fp32 parameter gradients that are otherwise added with floating-point atomics - as EXACT 64-bit integer
+ * sums (four bins of 40 bits per accumulator, 2^-96 ... 2^64; integer atomics), so every result is a bit-exact function of
+ * the call's inputs: independent of the order in which blocks or waves run, across repeats, processes and graph replays.
+ * With the mode off nothing changes.  The mode is process-wide host state, read when a call ISSUES its launches: a captured
+ * hipGraph keeps the mode it was captured in; producer and consumer of one buffer must be issued in the same mode.
+ *   - moments: the four fp64 copies of a [HRF_STAT_COPIES][2*C] slot are the four bins of each element - same buffers, same
+ *     zeroing; hrf_bn_finalize, hrf_bn_bwd_finalize and hrf_bn_pack read the bins instead of summing copies.  The finalize-
+ *     on-load prologues of the consumer kernels do not (the integer chains would cost the default-mode kernels registers):
+ *     in deterministic mode a BatchNorm is finalised by its own launch, as with HRF_FIN_ONLOAD=0.  A build with
+ *     HRF_STAT_COPIES < 4 cannot be switched on (HRF_ERR_ARG).
+ *   - fp32 gradient accumulators (dw / dbias / dgamma / dbeta / dkpad / dvpad / drpb arguments that are "+=" with atomics):
+ *     the caller owns SHADOW BINS, hrf_det_bins_bytes(n) bytes (32 per element, 8-byte aligned, zeroed once) for a range of n
+ *     floats, announced with hrf_det_register(base, n, bins) (bins == NULL: forget the range; a new range replaces the ones it
+ *     overlaps; at most 64 ranges).  In deterministic mode the kernels add into the bins of the target element - of copy 0
+ *     where the accumulator is replicated (`copy_stride`) - and leave the floats alone; hrf_det_resolve(g, n, stream) then
+ *     does g[i] += value(bins[i]) and returns the bins to zero (any mode; before hrf_fold_copies, a gradient exchange or the
+ *     optimizer read g).  Plain "+=" / stores of other kernels into the same floats are ordered by the stream as always.
+ *   - limits: at most 2^20 addends per accumulator and launch sequence; bits of an addend below 2^-96 are dropped (per addend,
+ *     so still order-independent); an addend that is not finite, or not below 2^64, makes the accumulator NaN.
+ *   - REFUSED in deterministic mode (HRF_ERR_ARG before any launch, outputs untouched) - never a silent unordered atomic:
+ *       a gradient accumulator outside every registered range;
+ *       an hrf_bn_fin_t / hrf_bn_bfin_t over REPLICATED moments (copies 0 / HRF_STAT_COPIES) handed to any consumer - hrf_conv_fwd
+ *       (_split, _packed), hrf_conv_bwd_data (_packed), hrf_dwconv_fwd / _bwd_data (_weight), hrf_attn_block_fwd / _bwd,
+ *       hrf_affine_act_res, hrf_fuse_sum; folded moments (copies 1) are plain doubles and are taken;
+ *       hrf_rpb_grad_all (its accumulator addresses sit in a device table: use hrf_rpb_grad per layer);
+ *       hrf_conv3_wgrad_wide with a bias gradient (the HRFPN neck's output convolutions);
+ *       hrf_gn_moments (GroupNorm);
+ *       hrf_p2p_exchange (SyncBN over more than one rank: the cross-rank order is out of scope; the one-rank path through
+ *       hrf_bn_pack / hrf_bn_finalize_packed works). */
+int hrf_set_deterministic(int on);
+int hrf_get_deterministic(void);
+long hrf_det_bins_bytes(long n);
+int hrf_det_register(float* base, long n, void* bins);
+int hrf_det_resolve(float* g, long n, void* stream);
+
 /* hipMemsetAsync on `stream` (the per-step zeroing of the replicated accumulators). */
 int hrf_memset(void* ptr, int value, long bytes, void* stream);
 
