@@ -1351,7 +1351,8 @@ class HipModule(nn.Module, EngineOwner):
     def _graph_key(self, inputs, record):
         flags = tuple(m.training for m in self._engine()._bns) if self._engine()._bns else ()
         return (self.training, record, tuple((tuple(t.shape), tuple(t.stride()), bool(t.requires_grad)) for t in inputs),
-                hash(flags), R.force_collectives(), self.sync_group is not None, int(self._lib_handle().hrf_get_deterministic()))
+                hash(flags), R.force_collectives(), self.sync_group is not None, getattr(self, 'matrix_mode', 'fp32'),
+                int(self._lib_handle().hrf_get_deterministic()))
 
     def _graph_entry(self, inputs, record):
         """-> the _GraphEntry to run this call through, or None for an eager call."""

@@ -249,6 +249,288 @@ __global__ __launch_bounds__(256) void conv3_pack_kernel(const float* w, int Cou
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// bf16x3 matrix mode of the same convolution (hrf_conv3_packed_bf16x3): every fp32 operand v is split into two bf16 values
+// hi = rne(v), lo = rne(v - hi) and a 32-channel slab of a tile is THREE v_mfma_f32_16x16x32_bf16 into the one fp32
+// accumulator - lo*hi, hi*lo, hi*hi (small terms first) - instead of eight v_mfma_f32_16x16x4_f32.  The dropped lo*lo term is
+// 2^-16 relative per product; DESIGN section 13 has the error model.  Same block / wave decomposition, weight ring, epilogue
+// and WN dispatch as conv3w_kernel; what differs:
+//   * 16-byte unit = 8 consecutive channels of one plane: a 32-channel slab of a pixel or of a weight row is 128 bytes =
+//     chunks 0..3 the hi plane (channels 8c..8c+7), chunks 4..7 the lo plane - exactly the bytes of the fp32 slab.  The MFMA
+//     takes k = 8 (lane >> 4) + j from lane element j, so a fragment of one plane is ONE ds_read_b128 of chunk q (+4);
+//   * weights arrive pre-split in that form (hrf_conv3_pack_bf16x3: the 128 bytes of row n, slab s sit where the fp32 pack
+//     has wp[tap][n][32 s ..]), so the weight ring is staged by the very same loads, stores and (row & 7) XOR swizzle;
+//   * activations are split while the halo is staged (global fp32 -> registers -> hi / lo chunks in LDS).  The halo pitch is
+//     128 bytes with chunk c of pixel p stored at chunk c ^ (p & 7): a ds_read_b128 lane group is 8 lanes of one q on
+//     pixels p0 + {0..3, 12..15} and 8 lanes of q ^ 1 on p0 + {4..11} - both cover every residue p & 7 once with alternating
+//     row halves of the 256-byte bank line, and q ^ 1 flips the chunk's low bit: 16 distinct 16-byte slots for ANY p0
+//     (the taps shift p0), as for the weight rows;
+//   * a step (tap x slab) is two halves of two channel tiles each: the weight fragments of the second half are fetched in
+//     the middle of the first half's MFMAs, the pixel fragments and first-half weight fragments of the NEXT step in the
+//     middle of the second half's (two alternating pixel-fragment sets: the loop is unrolled by two steps).
+#ifdef HRF_EMUL
+// round-to-nearest-even fp32 -> bf16 (bits), NaN kept quiet: what v_cvt_pk_bf16_f32 does
+inline uint16_t hrf_bf16_rne(float v) {
+  uint32_t u; std::memcpy(&u, &v, 4);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+inline float hrf_bf16_f32(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float v; std::memcpy(&v, &u, 4); return v; }
+inline void hrf_split1(float v, uint16_t& hi, uint16_t& lo) { hi = hrf_bf16_rne(v); lo = hrf_bf16_rne(v - hrf_bf16_f32(hi)); }
+// v0, v1 = 8 consecutive fp32 -> 8 hi and 8 lo bf16, element j in bits [16j, 16j+16) of the 16-byte unit
+inline void hrf_split8(hrf_f4 v0, hrf_f4 v1, hrf_f4& hi, hrf_f4& lo) {
+  uint16_t h[8], l[8];
+  for (int j = 0; j < 4; ++j) { hrf_split1(v0[j], h[j], l[j]); hrf_split1(v1[j], h[j + 4], l[j + 4]); }
+  std::memcpy(hi.d, h, 16); std::memcpy(lo.d, l, 16);
+}
+// v_mfma_f32_16x16x32_bf16: D = A(16x32) * B(32x16) + C; lane l supplies A[l&15][8(l>>4) + j] and B[8(l>>4) + j][l&15] in
+// element j of its 16-byte operands; result reg r of lane l = D[(l>>4)*4 + r][l&15] (the fp32 16x16 C/D layout).  The
+// products of two bf16 are exact in fp32; they are added in k order with fp32 roundings.  The staging buffer holds 16 bytes
+// per lane: A and B pass through it one after the other.
+inline hrf_f4 hrf_mfma16_bf16(hrf_f4 a, hrf_f4 b, hrf_f4 c) {
+  char* buf = static_cast<char*>(hrf_emul::wave_buf());
+  const int lane = hrf_emul::cur_lane, col = lane & 15, rq = lane >> 4;
+  uint16_t A[4][32], B[32];
+  std::memcpy(buf + 16 * lane, a.d, 16);
+  hrf_emul::sync_wave();
+  for (int r = 0; r < 4; ++r)
+    for (int q = 0; q < 4; ++q) std::memcpy(&A[r][8 * q], buf + 16 * (q * 16 + rq * 4 + r), 16);
+  hrf_emul::sync_wave();
+  std::memcpy(buf + 16 * lane, b.d, 16);
+  hrf_emul::sync_wave();
+  for (int q = 0; q < 4; ++q) std::memcpy(&B[8 * q], buf + 16 * (q * 16 + col), 16);
+  hrf_emul::sync_wave();
+  hrf_f4 d = c;
+  for (int r = 0; r < 4; ++r) {
+    float acc = c[r];
+    for (int k = 0; k < 32; ++k) acc = fmaf(hrf_bf16_f32(A[r][k]), hrf_bf16_f32(B[k]), acc);
+    d[r] = acc;
+  }
+  return d;
+}
+#else
+typedef __bf16 hrf_bf8 __attribute__((ext_vector_type(8)));
+__device__ __forceinline__ void hrf_split8(hrf_f4 v0, hrf_f4 v1, hrf_f4& hi, hrf_f4& lo) {
+  hrf_bf8 h, l;                                   // the casts compile to v_cvt_pk_bf16_f32 (round to nearest even)
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    h[j] = (__bf16)v0[j]; h[j + 4] = (__bf16)v1[j];
+    l[j] = (__bf16)(v0[j] - (float)h[j]); l[j + 4] = (__bf16)(v1[j] - (float)h[j + 4]);
+  }
+  hi = __builtin_bit_cast(hrf_f4, h); lo = __builtin_bit_cast(hrf_f4, l);
+}
+__device__ __forceinline__ hrf_f4 hrf_mfma16_bf16(hrf_f4 a, hrf_f4 b, hrf_f4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(hrf_bf8, a), __builtin_bit_cast(hrf_bf8, b), c, 0, 0, 0);
+}
+#endif
+
+constexpr int LPB = KS;       // bf16x3 halo pitch (floats): 128 bytes = 4 hi + 4 lo chunks, chunk c of pixel p at c ^ (p & 7)
+__device__ float g_zero8w[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+
+template <int WN>
+__global__ __launch_bounds__(NTHR) void conv3w_bf16x3_kernel(C3wArgs a) {
+  constexpr int NB = WN * 64;
+  constexpr int NHV = (NPIX * (KS / 8) + NTHR - 1) / NTHR;     // halo items (8 channels of a pixel) per thread (2)
+  HRF_DYN_SMEM(float, smem);
+  float* sIn = smem;                          // [NPIX * LPB]
+  float* sB = smem + NPIX * LPB;              // [3][NB * WP], as conv3w_kernel: chunk c of row n at c ^ (n & 7)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int i = lane & 15, q = lane >> 4;
+  const int chg = wave % WN, rg = wave / WN;
+  int t = blockIdx.x;
+  const int tx = t % a.tilesX; t /= a.tilesX;
+  const int ty = t % a.tilesY; const int b = t / a.tilesY;
+  const int y0 = ty * TH, x0 = tx * TW;
+  const int n0 = blockIdx.y * NB;
+  const bool wave_on = n0 + chg * 64 < a.N;
+
+  hrf_f4 acc[WN][4];
+#pragma unroll
+  for (int rr = 0; rr < WN; ++rr)
+#pragma unroll
+    for (int tt = 0; tt < 4; ++tt) acc[rr][tt] = hrf_f4{0.f, 0.f, 0.f, 0.f};
+
+  // ---- staging maps (padding lanes read the zero block with step 0: branch-free)
+  const float* hsrc[NHV]; int hstep[NHV], hdst[NHV];
+#pragma unroll
+  for (int e = 0; e < NHV; ++e) {
+    const int f = tid + e * NTHR;
+    const int pix = min(f >> 2, NPIX - 1), j = f & 3;
+    const int py = pix / IW, px = pix - py * IW;
+    const int gy = y0 - 1 + py, gx = x0 - 1 + px;
+    const bool ok = f < NPIX * 4 && (unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W;
+    hsrc[e] = ok ? a.x + ((long)(b * a.H + gy) * a.W + gx) * a.ldX + 8 * j : g_zero8w;
+    hstep[e] = ok ? KS : 0;
+    hdst[e] = f < NPIX * 4 ? pix * LPB + 4 * (j ^ (pix & 7)) : -1;      // hi chunk; the lo chunk is 16 floats away (c ^ 4)
+  }
+  const int wn = tid >> 3, wj = tid & 7;      // weight 16-byte unit e: row n = wn + 64*e, chunk wj (hi 0..3, lo 4..7)
+  hrf_f4 hpre[NHV][2], wpre[WN];
+  auto load_halo = [&](int slab) {
+#pragma unroll
+    for (int e = 0; e < NHV; ++e) {
+      hpre[e][0] = hrf_ld4(hsrc[e] + slab * hstep[e]);
+      hpre[e][1] = hrf_ld4(hsrc[e] + slab * hstep[e] + 4);
+    }
+  };
+  auto store_halo = [&]() {
+#pragma unroll
+    for (int e = 0; e < NHV; ++e) {
+      hrf_f4 hi, lo;
+      hrf_split8(hpre[e][0], hpre[e][1], hi, lo);
+      if (hdst[e] >= 0) { lds_st4(sIn + hdst[e], hi); lds_st4(sIn + (hdst[e] ^ 16), lo); }
+    }
+  };
+  const float* wrow[WN];
+#pragma unroll
+  for (int e = 0; e < WN; ++e) wrow[e] = a.wp + (long)min(n0 + wn + 64 * e, a.N - 1) * a.K + 4 * wj;   // rows past N feed switched-off waves
+  const long wtap = (long)a.N * a.K;
+  auto load_w = [&](int tap, int slab) {
+#pragma unroll
+    for (int e = 0; e < WN; ++e) wpre[e] = hrf_ld4(wrow[e] + tap * wtap + slab * KS);
+  };
+  auto store_w = [&](int ring) {
+    float* dst = sB + ring * (NB * WP);
+#pragma unroll
+    for (int e = 0; e < WN; ++e) lds_st4(dst + (wn + 64 * e) * WP + 4 * (wj ^ (wn & 7)), wpre[e]);
+  };
+  // fragments: [..][0] = hi plane, [..][1] = lo plane
+  hrf_f4 fa[2][WN][2], fb[2][2][2];           // fa[set][pixel row][plane]; fb[half][tile of the half][plane]
+  const int pbase = rg * WN * IW + i;         // halo pixel of (row rg*WN, col i) at tap (0, 0)
+  const float* bbase = sB + (chg * 64 + i) * WP;
+  const int bsw[2] = {4 * (q ^ (i & 7)), 4 * ((q + 4) ^ (i & 7))};
+  auto read_a = [&](int hp, auto set) {        // hp = dy * IW + dx
+#pragma unroll
+    for (int rr = 0; rr < WN; ++rr) {
+      const int p = pbase + hp + rr * IW;
+      const float* ap = sIn + p * LPB + 4 * (q ^ (p & 7));
+      fa[set][rr][0] = lds_ld4(ap);
+      fa[set][rr][1] = lds_ld4(sIn + p * LPB + 4 * ((q + 4) ^ (p & 7)));
+    }
+  };
+  auto read_b = [&](int ring, auto half) {
+    const float* bp = bbase + ring * (NB * WP) + half * 32 * WP;
+#pragma unroll
+    for (int t2 = 0; t2 < 2; ++t2)
+#pragma unroll
+      for (int pl = 0; pl < 2; ++pl) fb[half][t2][pl] = lds_ld4(bp + t2 * 16 * WP + bsw[pl]);
+  };
+  auto mma = [&](auto set, auto half, auto t2) {      // D[row = channel][col = pixel]: the weight fragment is the row operand
+#pragma unroll
+    for (int rr = 0; rr < WN; ++rr) {
+      hrf_f4 c = acc[rr][2 * half + t2];
+      c = hrf_mfma16_bf16(fb[half][t2][1], fa[set][rr][0], c);      // lo * hi
+      c = hrf_mfma16_bf16(fb[half][t2][0], fa[set][rr][1], c);      // hi * lo
+      c = hrf_mfma16_bf16(fb[half][t2][0], fa[set][rr][0], c);      // hi * hi
+      acc[rr][2 * half + t2] = c;
+    }
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+
+  const int nslab = a.K / KS, S = nslab * 9;
+  load_halo(0);
+  load_w(0, 0);
+  store_halo();
+  store_w(0);
+  load_w(1, 0);                                // S >= 9
+  store_w(1);
+  load_w(2, 0);                                // stays in registers until the top of step 0
+  __syncthreads();
+  if (wave_on) { read_a(0, I0{}); read_b(0, I0{}); HRF_WAIT_LDS(); }
+
+  int tap = 0, slab = 0;                       // step s
+  int dxn = 1, dyn = 0;                        // tap coordinates of step s+1
+  int tap3 = 3, slab3 = 0;                     // step s+3 (the weight tile fetched during step s)
+  int r0 = 0, r1 = 1, r2 = 2;                  // ring slots of steps s, s+1, s+2
+  int s = 0;
+  auto step = [&](auto set) {
+    constexpr int nset = 1 - decltype(set)::value;
+    if (s + 2 < S) store_w(r2);
+    if (s + 3 < S) load_w(tap3, slab3);
+    if (tap == 0 && slab + 1 < nslab) load_halo(slab + 1);
+    const bool boundary = tap == 8;            // the next step reads a new halo slab
+    const int hpn = dyn * IW + dxn;
+    if (wave_on) {
+      HRF_SCHED_FENCE();
+      mma(set, I0{}, I0{});
+      HRF_SCHED_FENCE();
+      read_b(r0, I1{});
+      HRF_SCHED_FENCE();
+      mma(set, I0{}, I1{});
+      HRF_SCHED_FENCE();                       // (the second half's weight fragments are a full tile row of MFMAs old when first used)
+      mma(set, I1{}, I0{});
+      HRF_SCHED_FENCE();
+      read_a(hpn, std::integral_constant<int, nset>{});       // unconditional; re-fetched below at a slab boundary
+      read_b(r1, I0{});
+      HRF_SCHED_FENCE();
+      mma(set, I1{}, I1{});
+      HRF_SCHED_FENCE();
+    }
+    __syncthreads();
+    if (boundary && s + 1 < S) {
+      store_halo();
+      __syncthreads();
+      if (wave_on) { read_a(hpn, std::integral_constant<int, nset>{}); HRF_WAIT_LDS(); }
+    }
+    tap = boundary ? 0 : tap + 1; slab += boundary ? 1 : 0;
+    if (++dxn == 3) { dxn = 0; if (++dyn == 3) dyn = 0; }
+    if (++tap3 == 9) { tap3 = 0; ++slab3; }
+    const int rt = r0; r0 = r1; r1 = r2; r2 = rt;
+    ++s;
+  };
+  while (s < S) {
+    step(I0{});
+    if (s < S) step(I1{});
+  }
+
+  // ---- epilogue (as conv3w_kernel): acc[rr][tt][r] = out(pixel (row rg*WN + rr, col i), channel chg*64 + tt*16 + 4q + r)
+  if (!wave_on) return;
+  const int x = x0 + i;
+#pragma unroll
+  for (int tt = 0; tt < 4; ++tt) {
+    const int ch = n0 + chg * 64 + tt * 16 + 4 * q;
+    hrf_f4 bv = hrf_f4{0.f, 0.f, 0.f, 0.f};
+    if (a.bias != nullptr) bv = hrf_ld4(a.bias + ch);
+#pragma unroll
+    for (int rr = 0; rr < WN; ++rr) {
+      const int y = y0 + rg * WN + rr;
+      if (y < a.H && x < a.W) {
+        float* o = a.y + ((long)(b * a.H + y) * a.W + x) * a.ldY + ch;
+        hrf_f4 v = acc[rr][tt];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += bv[r];
+        if (a.accumulate) {
+          const hrf_f4 p = hrf_ld4(o);
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] += p[r];
+        }
+        hrf_st4(o, v);
+      }
+    }
+  }
+}
+
+// the bf16x3 pack: element (tap, n, k) of the tap-major pack as two bf16; the 32-channel slab s of row (tap, n) occupies the
+// 128 bytes where the fp32 pack has its 32 floats: bf16 [0, 32) = hi of channels 32 s .. 32 s + 31, bf16 [32, 64) = lo
+__global__ __launch_bounds__(256) void conv3_pack_bf16x3_kernel(const float* w, int Cout, int Cin, int dir, unsigned short* wp) {
+  const int N = dir ? Cin : Cout, K = dir ? Cout : Cin;
+  const long total = 9L * N * K;
+  for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+    const int k = (int)(e % K);
+    const long r = e / K;
+    const int n = (int)(r % N), tap = (int)(r / N);
+    const float v = dir ? w[((long)k * Cin + n) * 9 + 8 - tap] : w[((long)n * Cin + k) * 9 + tap];
+    unsigned short* o = wp + 2 * (r * K + (k & ~(KS - 1))) + (k & (KS - 1));
+#ifdef HRF_EMUL
+    hrf_split1(v, o[0], o[KS]);
+#else
+    const __bf16 hi = (__bf16)v, lo = (__bf16)(v - (float)hi);
+    o[0] = __builtin_bit_cast(unsigned short, hi);
+    o[KS] = __builtin_bit_cast(unsigned short, lo);
+#endif
+  }
+}
+
 
 // ------------------------------------------------------------------------------------------------------------------
 // Weight gradient of the same convolutions: dW[co][ci][tap] += sum_pix dY[pix][co] * X[pix + tap][ci].
@@ -578,7 +860,44 @@ int launch_w(C3wArgs a, void* stream) {
   return hrf_check_launch();
 }
 
+template <int WN>
+int launch_w_bf16x3(C3wArgs a, void* stream) {
+  constexpr size_t smem = (size_t)(NPIX * LPB + 3 * WN * 64 * WP) * sizeof(float);
+#ifndef HRF_EMUL
+  static std::atomic<unsigned> lds_set{0u};
+  if (hrf_dyn_lds_once(lds_set, reinterpret_cast<const void*>(&conv3w_bf16x3_kernel<WN>), (int)smem) != HRF_OK) return HRF_ERR_LAUNCH;
+#endif
+  const dim3 grid(a.tilesX * a.tilesY * a.B, hrf_cdiv(a.N, WN * 64));
+  HRF_LAUNCH((conv3w_bf16x3_kernel<WN>), grid, dim3(NTHR), smem, stream, a);
+  return hrf_check_launch();
+}
+
 }  // namespace
+
+extern "C" int hrf_conv3_bf16x3_supported(int K, int N) {
+  return K > 0 && N > 0 && K % KS == 0 && N % 64 == 0 ? 1 : 0;
+}
+
+extern "C" int hrf_conv3_pack_bf16x3(const float* w, int Cout, int Cin, int dir, float* wp, void* stream) {
+  const long total = 9L * Cout * Cin;
+  if (total <= 0) return HRF_OK;
+  if ((dir ? Cout : Cin) % KS != 0) return HRF_ERR_ARG;         // the planes are laid out per 32-channel slab of K
+  const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+  HRF_LAUNCH(conv3_pack_bf16x3_kernel, dim3(grid), dim3(256), 0, stream, w, Cout, Cin, dir, reinterpret_cast<unsigned short*>(wp));
+  return hrf_check_launch();
+}
+
+extern "C" int hrf_conv3_packed_bf16x3(const float* x, int ldX, const float* wp, const float* bias, float* y, int ldY,
+                                       int accumulate, int B, int H, int W, int K, int N, void* stream) {
+  if (!hrf_conv3_bf16x3_supported(K, N)) return HRF_ERR_ARG;
+  if (B <= 0 || H <= 0 || W <= 0) return HRF_OK;
+  C3wArgs a{x, ldX, wp, bias, y, ldY, accumulate, B, H, W, K, N, hrf_cdiv(W, TW), hrf_cdiv(H, TH)};
+  const long tiles = (long)a.tilesX * a.tilesY * B;
+  // (the dispatch of hrf_conv3_packed)
+  int wn = (N % 256 == 0 && tiles >= 128) ? 4 : ((N % 128 == 0 && tiles >= 32) ? 2 : 1);
+  if (g_force_wn == 1 || (g_force_wn == 4 && N % 256 == 0) || (g_force_wn == 2 && N % 128 == 0)) wn = g_force_wn;
+  return wn == 4 ? launch_w_bf16x3<4>(a, stream) : (wn == 2 ? launch_w_bf16x3<2>(a, stream) : launch_w_bf16x3<1>(a, stream));
+}
 
 extern "C" int hrf_conv3_pack(const float* w, int Cout, int Cin, int dir, float* wp, void* stream) {
   const long total = 9L * Cout * Cin;

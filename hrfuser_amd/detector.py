@@ -36,6 +36,17 @@ class FeatureExtractor(nn.Module):
     def with_neck(self):
         return hasattr(self, 'neck') and self.neck is not None                                      # base.py:27-29
 
+    @property
+    def matrix_mode(self):
+        """The neck's matrix mode (HRFPN.matrix_mode); 'fp32' without a neck."""
+        return self.neck.matrix_mode if self.with_neck else 'fp32'
+
+    def set_matrix_mode(self, mode):
+        """HRFPN.set_matrix_mode of the neck (the backbone's engines are fp32 in either mode)."""
+        if not self.with_neck:
+            raise ValueError('FeatureExtractor.set_matrix_mode: no neck - the matrix mode belongs to HRFPN')
+        self.neck.set_matrix_mode(mode)
+
     def extract_feat(self, img, mod_imgs=None):
         """two_stage.py:76-84."""
         if mod_imgs is not None:
@@ -73,6 +84,7 @@ class ExtractTrainer:
         self.tn = Trainer(feats.neck, group=group, world_size=world_size, **opt)
         self.group, self.world = group, world_size
         self.graph = None
+        self._graph_mm = None                # the neck's matrix mode the graph was captured in
 
     def _step_impl(self, x, mods, cots):
         net, neck = self.feats.backbone, self.feats.neck
@@ -128,9 +140,14 @@ class ExtractTrainer:
         with R.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
             self._graph_outs = self._step_impl(x, mods, cots)
         self.graph = g
+        self._graph_mm = self.feats.neck.matrix_mode
         return g
 
     def replay(self):
+        if self._graph_mm != self.feats.neck.matrix_mode:
+            # (a graph replays the launches it recorded: the other mode's kernels are never reached through it)
+            raise _lib.HRFuserHipError(f'ExtractTrainer.replay: this graph was captured in matrix mode {self._graph_mm!r}, the '
+                                       f'neck is in {self.feats.neck.matrix_mode!r} now (set_matrix_mode) - capture again')
         self.graph.replay()
 
 

@@ -23,6 +23,13 @@ from .registry import NECKS
 
 
 _WIDE = os.environ.get('HRF_NECK_WIDE', '1') != '0'       # 0: route the 3x3 convolutions through hrf_conv_fwd instead
+MATRIX_MODES = ('fp32', 'bf16x3')
+
+
+def _check_matrix_mode(mode, what):
+    if mode not in MATRIX_MODES:
+        raise ValueError(f'{what}: matrix mode {mode!r} is not one of {MATRIX_MODES}')
+    return mode
 
 
 class _ConvModule(nn.Module):
@@ -43,8 +50,12 @@ def _conv3_wide(ctx, x, conv):
     Cout = w.shape[0]
     out = R.Act(R._new((B, H, W, Cout), x.t.device))
     wp = R._new((9 * Cout * C,), x.t.device)
-    L.hrf_conv3_pack(w, Cout, C, 0, wp, s)
-    L.hrf_conv3_packed(x.t, C, wp, b, out.t, Cout, 0, B, H, W, C, Cout, s)
+    # matrix mode of the owning neck (HRFPN.set_matrix_mode), fixed at the forward: the backward of this tape follows it.
+    # bf16x3: the same two launches on the bf16 matrix cores (split operands, three products); the pack has the same size
+    bf = getattr(ctx.owner, 'matrix_mode', 'fp32') == 'bf16x3'
+    pack, conv = (L.hrf_conv3_pack_bf16x3, L.hrf_conv3_packed_bf16x3) if bf else (L.hrf_conv3_pack, L.hrf_conv3_packed)
+    pack(w, Cout, C, 0, wp, s)
+    conv(x.t, C, wp, b, out.t, Cout, 0, B, H, W, C, Cout, s)
 
     def bwd():
         if out.grad is None:
@@ -62,9 +73,9 @@ def _conv3_wide(ctx, x, conv):
                     out.grad, Cout, 0, None, None, None, None, x.t, *strides, B, H, W, C, 3, 1, Cout,
                     R.TF_NONE, None, None, None, w.grad, bgrad, ctx.stream))
         if x.needs_grad:
-            L.hrf_conv3_pack(w, Cout, C, 1, wp, s)                 # the forward pack is dead by now: reuse its buffer
+            pack(w, Cout, C, 1, wp, s)                             # the forward pack is dead by now: reuse its buffer
             g, acc = x.grad_target()
-            L.hrf_conv3_packed(out.grad, Cout, wp, None, g, C, acc, B, H, W, Cout, C, s)
+            conv(out.grad, Cout, wp, None, g, C, acc, B, H, W, Cout, C, s)
     ctx.push(bwd)
     return out
 
@@ -115,6 +126,23 @@ class HRFPN(HipModule):
         self.reduction_conv = _ConvModule(sum(in_channels), out_channels, 1)
         self.fpn_convs = nn.ModuleList(_ConvModule(out_channels, out_channels, 3, stride, 1)
                                        for _ in range(num_outs))
+        self.__dict__['_matrix_mode'] = _check_matrix_mode(os.environ.get('HRF_MATRIX_MODE', '') or 'fp32', 'HRF_MATRIX_MODE')
+
+    @property
+    def matrix_mode(self):
+        """'fp32' (default) or 'bf16x3': how the wide 3x3 engine multiplies (set_matrix_mode)."""
+        return self.__dict__.get('_matrix_mode', 'fp32')
+
+    def set_matrix_mode(self, mode):
+        """'fp32': every matrix product on fp32 MFMA (the default; the initial value comes from HRF_MATRIX_MODE).
+        'bf16x3': the 3x3 output convolutions that run on the wide packed engine (forward and data gradient) split their
+        fp32 operands into two bf16 parts each and sum three products on the bf16 matrix cores in fp32 - ~5e-6 relative to
+        an fp64 convolution instead of ~4e-7.  Weight gradients, the reduction convolution and every
+        convolution the wide engine does not take stay fp32.  The mode is read when a forward pass issues its launches:
+        the backward of that pass follows it, and a captured step replays the mode it was captured in (Trainer /
+        ExtractTrainer refuse to replay a graph of the other mode)."""
+        self.__dict__['_matrix_mode'] = _check_matrix_mode(mode, 'HRFPN.set_matrix_mode')
+        self.reset_graphs()
 
     def init_weights(self):
         """mmcv caffe2_xavier_init = kaiming_uniform(a=1, fan_in, leaky_relu), bias 0 (init_cfg, hrfpn.py:41)."""

@@ -101,6 +101,12 @@ def work_model(name, a):
         return f'attn_block_bwd_kernel<{C}, {heads}>', 3.0 * fwd, by
     if name == 'hrf_rpb_grad':
         return 'rpb_grad_kernel', 0.0, f4 * a['nwin'] * a['heads'] * 49 * 49
+    if name == 'hrf_conv3_packed_bf16x3':
+        # bf16x3 matrix mode of the wide 3x3 engine: the algorithmic work of the convolution (one multiply-add per term, whatever
+        # the three split products cost - MFMA_ROOF prices those) and its fp32 rows and pack
+        M = float(a['B']) * a['H'] * a['W']
+        return ('conv3w_bf16x3_kernel', 2.0 * 9 * M * a['K'] * a['N'],
+                f4 * (M * a['K'] + 9.0 * a['K'] * a['N'] + M * a['N'] * (1 + bool(a['accumulate']))))
     rc = None
     if 'rows' in a and 'C' in a:
         rc = float(a['rows']) * a['C']
@@ -447,8 +453,14 @@ def merged_launch_counts(trainer, x, mods, cots):
     return c1[0] - c0[0], c1[1] - c0[1]
 
 
+# matrix roof of a kernel key relative to the fp32-MFMA peak the callers pass in: bf16 MFMA runs at 16x the fp32 rate on gfx950
+# and a bf16x3 kernel spends three bf16 products per algorithmic one
+MFMA_ROOF = {'conv3w_bf16x3_kernel': 16.0 / 3.0}
+
+
 def _row(key, t, peak_f, peak_b):
     n, sec, fl, by, steps = t
+    peak_f = peak_f * MFMA_ROOF.get(key, 1.0)
     bound = 'mfma' if (fl / peak_f) > (by / peak_b) else 'hbm'
     if bound == 'mfma':
         ach, peak, unit = fl / sec / 1e12, peak_f / 1e12, 'TFLOP/s'

@@ -39,6 +39,7 @@ class Trainer:
         self._ready = False
         self.graph = None
         self._graph_det = None               # (deterministic mode, engine's det_epoch) the graph was captured in
+        self._graph_mm = None                # matrix mode of the net (HRFPN.set_matrix_mode) the graph was captured in
         self.collectives_per_step = 0
 
     # -------------------------------------------------------------------------------------------
@@ -183,6 +184,7 @@ class Trainer:
             self._graph_outs = self._step_impl(x, mods, cots)
         self.graph = g
         self._graph_det = (int(self.net._lib_handle().hrf_get_deterministic()), self.net._engine().det_epoch)
+        self._graph_mm = getattr(self.net, 'matrix_mode', 'fp32')
         px = self._exchange()
         if px is not None:
             px.pin()                     # the graph's exchange launches carry the context's inbox / flag / counter pointers
@@ -193,6 +195,9 @@ class Trainer:
         if self._graph_det != (int(self.net._lib_handle().hrf_get_deterministic()), self.net._engine().det_epoch):
             raise _lib.HRFuserHipError('Trainer.replay: the deterministic mode was switched since this graph was captured '
                                        '(net.set_deterministic) - capture again')
+        if self._graph_mm != getattr(self.net, 'matrix_mode', 'fp32'):
+            raise _lib.HRFuserHipError(f'Trainer.replay: this graph was captured in matrix mode {self._graph_mm!r}, the net is in '
+                                       f'{self.net.matrix_mode!r} now (set_matrix_mode) - capture again')
         self.graph.replay()
         self._poll_exchange()
 

@@ -459,6 +459,23 @@ int hrf_avg_pool_bwd(const float* g, int B, int H, int W, int C, int k, float* d
 int hrf_conv3_pack(const float* w, int Cout, int Cin, int dir, float* wp, void* stream);
 int hrf_conv3_packed(const float* x, int ldX, const float* wp, const float* bias, float* y, int ldY, int accumulate,
                      int B, int H, int W, int K, int N, void* stream);
+/* bf16x3 matrix mode of the same convolution: the bf16 matrix cores with fp32-level accuracy.  Every fp32 operand v is split
+ * into two bf16 values, hi = rne(v) and lo = rne(v - hi) (round to nearest even), and every product is computed as
+ * lo*hi + hi*lo + hi*hi on v_mfma_f32_16x16x32_bf16, accumulated in fp32; bias and accumulate are applied in the fp32 epilogue.
+ * Accuracy: relmax against an fp64 convolution 4e-6 .. 6e-6 on unit-variance data (fp32 kernel: 2e-7 .. 5e-7; one bf16 product
+ * alone: 2e-3) - the dropped lo*lo term and the rounding of lo, 2^-16 .. 2^-17 per product; DESIGN section 13.
+ *   hrf_conv3_pack_bf16x3    same `dir` semantics and the same 9*Cout*Cin*4 bytes as hrf_conv3_pack, holding bf16 planes: with
+ *                    p = the fp32 pack [tap][n][k], the 32-channel slab s of row (tap, n) is 64 bf16 at the byte offset of
+ *                    p[tap][n][32 s]: bf16 [0, 32) = hi(p[tap][n][32 s + j]), bf16 [32, 64) = lo(p[tap][n][32 s + j]), i.e. the
+ *                    buffer viewed as bf16 is [9][N][K/32][2 (hi, lo)][32].  K (Cin for dir 0, Cout for dir 1) % 32 == 0.
+ *   hrf_conv3_packed_bf16x3  the contract of hrf_conv3_packed (fp32 rows in, fp32 rows out, K % 32 == 0, N % 64 == 0, columns
+ *                    of y beyond N untouched) on a pack of hrf_conv3_pack_bf16x3; an unsupported shape returns HRF_ERR_ARG
+ *                    before any launch.  No atomics: bit-reproducible, independent of hrf_set_deterministic.
+ *   hrf_conv3_bf16x3_supported  1 when (K, N) is a shape hrf_conv3_packed_bf16x3 accepts, else 0; no launch. */
+int hrf_conv3_pack_bf16x3(const float* w, int Cout, int Cin, int dir, float* wp, void* stream);
+int hrf_conv3_packed_bf16x3(const float* x, int ldX, const float* wp, const float* bias, float* y, int ldY, int accumulate,
+                            int B, int H, int W, int K, int N, void* stream);
+int hrf_conv3_bf16x3_supported(int K, int N);
 /*   hrf_conv3_wgrad_wide  dW[co][ci][3][3] += sum_pix dY[pix][co] * x[pix + tap][ci],  dbias[co] += sum_pix dY[pix][co]
  *                    (aten convolution_backward's grad_weight / grad_bias of the same convolution; OIHW dW;
  *                    Cout % 128 == 0, Cin % 64 == 0; dbias nullable).  The pixel-split partial sums pass through
