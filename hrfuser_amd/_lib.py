@@ -177,6 +177,14 @@ def lib():
     return _LIB
 
 
+def attn_fwd_form(C):
+    """Wave-group form (1 / 2 / 4) a hrf_attn_block_fwd launch of width C takes now: hrf_debug_knob(37, C), a query whose return
+    value is the answer, not a status (0: the form forced by knob 36 is not built for this width)."""
+    l = lib()
+    l = getattr(l, '_lib', l)                       # (a profiling wrapper around the library)
+    return int(l._dll.hrf_debug_knob(37, int(C)))
+
+
 def stream_ptr():
     """hipStream_t of torch's current stream (0 when no GPU context: emulation tests only)."""
     if torch.cuda.is_available():

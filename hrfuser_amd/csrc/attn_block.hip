@@ -77,7 +77,8 @@ __device__ __forceinline__ int ab_tok_pixel(const hrf_attn_block_t& a, int b, in
 #endif
 // acc[t] (t < NT) += W[n0 + 16t + i][.] . rows[tok0 + j][.] over K: D[n][token], lane (j, q) ends up holding the four
 // output channels n0 + 16t + 4q + r of token tok0 + j.  W is [N][K] row-major in global memory, rows an LDS tile.
-template <int K, int NT>
+// TS: the tiles of one wave lie TS tiles apart (n0 + 16 TS t: the wave-group forms of the forward kernel), 1 = adjacent.
+template <int K, int NT, int TS = 1>
 __device__ __forceinline__ void wave_gemm(const float* W, int n0, int N, const float* rows, int pitch, int tok0, int lane,
                                           hrf_f4* acc) {
   const int i = lane & 15, q = lane >> 4;
@@ -90,7 +91,7 @@ __device__ __forceinline__ void wave_gemm(const float* W, int n0, int N, const f
     hrf_f4 wv[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-      const int n = n0 + 16 * t + i;
+      const int n = n0 + 16 * TS * t + i;
       wv[t] = ld_sel(kfull, W, (long)n * K + kbase, n < N ? kval : 0);
     }
     float bv[4];
@@ -105,14 +106,14 @@ __device__ __forceinline__ void wave_gemm(const float* W, int n0, int N, const f
   }
 }
 
-// bias rows into the accumulators (D = A*B + C): acc[t][r] = bias[n0 + 16t + 4q + r]
-template <int NT>
+// bias rows into the accumulators (D = A*B + C): acc[t][r] = bias[n0 + 16 TS t + 4q + r]
+template <int NT, int TS = 1>
 __device__ __forceinline__ void acc_bias(const float* bias, int n0, int N, int lane, hrf_f4* acc) {
   const int q = lane >> 4;
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
-    const int nb = n0 + 16 * t + 4 * q;
-    acc[t] = ld_sel(n0 + 16 * (t + 1) <= N, bias, nb, bias != nullptr ? N - nb : 0);
+    const int nb = n0 + 16 * TS * t + 4 * q;
+    acc[t] = ld_sel(n0 + 16 * (TS * t + 1) <= N, bias, nb, bias != nullptr ? N - nb : 0);
   }
 }
 
@@ -131,19 +132,22 @@ __device__ __forceinline__ void acc_bias_l(const float* sB, int n0, int lim, int
 
 // Stage the 49 rows of a window (zeros for tokens outside the image and for rows 49..63) and LayerNorm them in place.
 // Four lanes cooperate on one token; all global loads of a thread are issued before its first LDS store.
-// `tail` (uniform): the rows are FORMED here - x = x[.] + rs * GELU(sTs[c] * traw[.] + sTs[C + c]), the CrossFFN tail of the
+// `tail` (uniform): the rows are FORMED here - x = x[.] + rs * GELU(sSc[c] * traw[.] + sSh[c]), the CrossFFN tail of the
 // preceding block (hrformer.py:371-372) - and written to xout for the residual add of this launch and for the backward.
-template <int C>
+// sSc / sSh: scale and shift of the tail's BatchNorm.  NTHR threads stage (the wave-group forms of the forward kernel: every
+// element is the same value whichever thread moves it); the LayerNorm stays on the first 256 - token t in lanes 4t..4t+3,
+// the same per-lane channel order and the same shuffles in every form.
+template <int C, int NTHR = 256>
 __device__ __forceinline__ void stage_ln_rows(const hrf_attn_block_t& a, const float* x, const float* gam, const float* bet,
                                               int b, int wy, int wx, float* sX, const int* sPix,
-                                              const float* traw = nullptr, const float* sTs = nullptr, float rs = 1.f,
+                                              const float* traw = nullptr, const float* sSc = nullptr, const float* sSh = nullptr, float rs = 1.f,
                                               float* xout = nullptr) {
   constexpr int PC = C + 1;
-  constexpr int NE = (NTOK * C + 255) / 256;
+  constexpr int NE = (NTOK * C + NTHR - 1) / NTHR;
   float v[NE];
 #pragma unroll
   for (int u = 0; u < NE; ++u) {
-    const int e = threadIdx.x + 256 * u;
+    const int e = threadIdx.x + NTHR * u;
     const int ec = e < NTOK * C ? e : 0;
     const int j = ec / C, c = ec - j * C;
     const int pix = sPix[j];
@@ -154,7 +158,7 @@ __device__ __forceinline__ void stage_ln_rows(const hrf_attn_block_t& a, const f
     float rw[NE];
 #pragma unroll
     for (int u = 0; u < NE; ++u) {
-      const int e = threadIdx.x + 256 * u;
+      const int e = threadIdx.x + NTHR * u;
       const int ec = e < NTOK * C ? e : 0;
       const int j = ec / C, c = ec - j * C;
       const int pix = sPix[j];
@@ -162,21 +166,22 @@ __device__ __forceinline__ void stage_ln_rows(const hrf_attn_block_t& a, const f
     }
 #pragma unroll
     for (int u = 0; u < NE; ++u) {
-      const int e = threadIdx.x + 256 * u;
+      const int e = threadIdx.x + NTHR * u;
       const int ec = e < NTOK * C ? e : 0;
       const int j = ec / C, c = ec - j * C;
       const int pix = sPix[j];
-      const float xv = v[u] + rs * hrf_gelu(fmaf(rw[u], sTs[c], sTs[C + c]));
+      const float xv = v[u] + rs * hrf_gelu(fmaf(rw[u], sSc[c], sSh[c]));
       v[u] = pix >= 0 ? xv : 0.f;
       if (e < NTOK * C && pix >= 0) xout[(long)pix * C + c] = xv;
     }
   }
 #pragma unroll
   for (int u = 0; u < NE; ++u) {
-    const int e = threadIdx.x + 256 * u;
+    const int e = threadIdx.x + NTHR * u;
     if (e < NTOK * C) { const int j = e / C; sX[j * PC + (e - j * C)] = v[u]; }
   }
   __syncthreads();
+  if (NTHR > 256 && threadIdx.x >= 256) return;                     // (whole waves)
   const int t = threadIdx.x >> 2, part = threadIdx.x & 3;           // token, quarter of its channels
   const float* row = sX + t * PC;
   float s = 0.f;
@@ -271,14 +276,64 @@ struct AbFwdArgs {
 // K-steps of the token contractions whose four rows (tokens 16t + 4q + r, q = 0..3) all lie beyond the 49 tokens of a window:
 // t = 3, r = 1..3 (tokens 49 ... 63).  Their operands are exact zeros (P and dS of pad keys / queries): skipped, 13 of 16 steps remain
 #define AB_PADK(t, r) ((t) == 3 && (r) > 0)
-template <int C, int HEADS>
-__global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs> grp) {
+
+// Wave groups (G = 1, 2, 4).  A launch of this kernel lasts as long as ONE workgroup (12 - 48 windows on 256 CUs at the wide
+// widths): what it costs is the length of the chain inside a window, and with four waves that chain is as long as the window
+// is wide - wave w computes every channel tile of its 16 tokens and walks every head.  The G form runs 4 G waves: wave
+// (tt, g) = (wave & 3, wave >> 2) keeps token tile tt and owns, in each phase, the channel tiles t of the projections and of
+// out_proj with t % G == g, the heads h with h % G == g and the 16-channel tiles of the CrossFFN head with tile % G == g.
+// Every output element of every GEMM and every (token tile, head) of the attention core is still produced by one wave in the
+// same k order, so out / h1 / x_out are BIT-EQUAL to the G = 1 form.  The one quantity that needs a whole x' row is the
+// LayerNorm_2 statistic: the waves of a token tile put their x' tiles into the X tile, and after a barrier EVERY wave reads
+// the whole row back in the per-lane (t, r) order of the G = 1 form and runs the same shuffles - no partial sums are combined.
+// The LN_2 rows go to the Q tile (its attention output is dead behind the same barrier), sStat keeps [token tile][2][4C].
+//
+// LDS, bytes (dynamic tiles + slack + RPB table | static sPix + tail coefficients; the limit is 163 840):
+//   <18,1>   12 672 (weights) + 19 456 + 128 +   704 | 256 +   144 =  33 360      <78,2>    80 896 + 128 + 1 408 | 256 + 624 =  83 312
+//   <36,2>   41 472 (weights) + 37 888 + 128 + 1 408 | 256 +   288 =  81 440      <156,4>  160 768 +   0 + 2 816 | 256 +   0 = 163 840
+//   <72,4>                      74 752 + 128 + 2 816 | 256 +   576 =  78 528
+//   <144,8>                    148 480 + 128 + 5 632 | 256 + 1 152 = 155 648
+// <156,4> fits by aliasing alone (TIGHT): the tail's scale | shift live in rows 0 and 1 of the V tile, which is first written
+// by the v projection, after the only staging that reads them; and the 32 floats behind V (its fragments are read 16 columns
+// wide, up to 13 floats past the last row - products that land in output columns >= D, which are never stored) are the first
+// floats of the RPB table, which follows V directly: they only have to be finite.  312 / 8 and 624 / 16: four tiles do not fit.
+template <int C, bool TIGHT> struct AbTailCoef {
+  static __device__ __forceinline__ float* get(float*) { __shared__ float sTs[2 * C]; return sTs; }
+  static constexpr int PITCH = C;
+};
+template <int C> struct AbTailCoef<C, true> {
+  static __device__ __forceinline__ float* get(float* sV) { return sV; }
+  static constexpr int PITCH = C + 1;
+};
+template <int C, int HEADS> struct AbFwdLds {
+  static constexpr bool WL = C <= 36;
+  static constexpr int TILES = 4 * 64 * (C + 1), TABLE = HEADS * 176, WEIGHTS = WL ? 8 * C * ((C + 3) & ~3) : 0;
+  static constexpr bool TIGHT = (size_t)(WEIGHTS + TILES + 32 + TABLE + 64 + 2 * C) * sizeof(float) > 160 * 1024;
+  static constexpr int SLACK = TIGHT ? 0 : 32;
+  static constexpr size_t DYN = (size_t)(WEIGHTS + TILES + SLACK + TABLE) * sizeof(float);
+  static_assert(DYN + (64 + (TIGHT ? 0 : 2 * C)) * sizeof(float) <= 160 * 1024, "four [64][C+1] tiles do not fit the LDS");
+};
+// 16-channel tiles of the CrossFFN head per pass of a wave: at most 9 (accumulators + weight fragments; 5 at 16 waves, where a
+// wave has 128 registers: 9 spilled at 144 channels), passes of equal length
+constexpr int ab_ffn_tiles(int C, int G) {
+  const int cap = G == 4 ? 5 : 9;
+  const int per = ((4 * C + 15) / 16 + G - 1) / G, passes = (per + cap - 1) / cap;
+  return (per + passes - 1) / passes;
+}
+
+template <int C, int HEADS, int G>
+__global__ __launch_bounds__(256 * G) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs> grp) {
+  static_assert(HEADS % G == 0 && (G == 1 || G == 2 || G == 4), "wave groups: 1, 2 or 4, dividing the heads");
   const hrf_attn_block_t& a = grp.sel().a;
   const hrf_bn_fin_t& tfin = grp.sel().fin;
   constexpr int D = C / HEADS, PC = C + 1, CT = (C + 15) / 16, PW = (C + 3) & ~3;
   constexpr int KSD = (D + 3) / 4, DT = (D + 15) / 16;
   constexpr int TILE = 64 * PC;
-  constexpr bool WL = C <= 36;            // weights staged in LDS (8*C*PW floats in front of the tiles)
+  constexpr int NTHR = 256 * G;           // threads of the workgroup
+  constexpr int CTG = (CT + G - 1) / G;   // channel tiles of a wave: g, g + G, ...
+  using Lds = AbFwdLds<C, HEADS>;
+  constexpr bool WL = Lds::WL;            // weights staged in LDS (8*C*PW floats in front of the tiles)
+  static_assert(!WL || G == 1, "the LDS-weight widths have no group form");
   HRF_DYN_SMEM(float, smem);
   float* sW1 = smem;                      // [4C][PW] w1, [C][PW] wo / wq / wk / wv  (WL only)
   float* sWo = sW1 + 4 * C * PW;
@@ -286,29 +341,31 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
   float* sWk = sWq + C * PW;
   float* sWv = sWk + C * PW;
   float* sX = smem + (WL ? 8 * C * PW : 0);   // source rows -> LayerNorm'd rows -> x' -> LN_2(x')
-  float* sQ = sX + TILE;                  // scaled q -> attention output o
+  float* sQ = sX + TILE;                  // scaled q -> attention output o (-> LN_2(x'), G > 1)
   float* sK = sQ + TILE;
-  float* sV = sK + TILE;                  // (+32 floats of slack behind it: V fragments are read 16 columns wide)
-  float* sT = sV + TILE + 32;             // [HEADS][176] relative position bias of every head
-  float* sStat = sK;                      // [4][2][4C] BatchNorm moments of h1 per wave: aliases K / V once attention is done
+  float* sV = sK + TILE;                  // (+32 floats of slack behind it: V fragments are read 16 columns wide; TIGHT: the table)
+  float* sT = sV + TILE + Lds::SLACK;     // [HEADS][176] relative position bias of every head
+  float* sStat = sK;                      // [4][2][4C] BatchNorm moments of h1 per token tile: aliases K / V once attention is done
   __shared__ int sPix[64];
-  __shared__ float sTs[2 * C];            // scale | shift of the tail's BatchNorm
+  float* sTs = AbTailCoef<C, Lds::TIGHT>::get(sV);   // scale | shift of the tail's BatchNorm
+  constexpr int TSP = AbTailCoef<C, Lds::TIGHT>::PITCH;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int i = lane & 15, q = lane >> 4;
+  const int tt = G == 1 ? wave : (wave & 3), g = G == 1 ? 0 : (wave >> 2);   // token tile, wave group
   const int win = blockIdx.x;
   const int wx = win % a.nWw, wy = (win / a.nWw) % a.nWh, b = win / (a.nWw * a.nWh);
   const bool tail = a.tail_raw != nullptr;
   if (tid < 64) sPix[tid] = tid < NTOK ? ab_tok_pixel(a, b, wy, wx, tid) : -1;
   if (tail) {
-    if (tfin.stats != nullptr) hrf_bn_fin_onload(tfin, sTs, sTs + C, tid, 256, blockIdx.x == 0);
-    else for (int e = tid; e < C; e += 256) { sTs[e] = a.tail_scale[e]; sTs[C + e] = a.tail_shift[e]; }
+    if (tfin.stats != nullptr) hrf_bn_fin_onload(tfin, sTs, sTs + TSP, tid, NTHR, blockIdx.x == 0);
+    else for (int e = tid; e < C; e += NTHR) { sTs[e] = a.tail_scale[e]; sTs[TSP + e] = a.tail_shift[e]; }
   }
-  for (int e = tid; e < 64 * PC; e += 256) sX[e] = 0.f;
-  for (int e = tid; e < HEADS * 176; e += 256) {
+  for (int e = tid; e < 64 * PC; e += NTHR) sX[e] = 0.f;
+  for (int e = tid; e < HEADS * 176; e += NTHR) {
     const int h = e / 176, k = e - h * 176;
     sT[e] = k < 169 ? a.rpb[k * HEADS + h] : 0.f;
   }
-  if (tid < 32) sV[TILE + tid] = 0.f;
+  if (Lds::SLACK > 0 && tid < 32) sV[TILE + tid] = 0.f;
   if (tid < 64) { sQ[tid * PC + C] = 0.f; sK[tid * PC + C] = 0.f; sV[tid * PC + C] = 0.f; }   // pitch column: read (masked) by the last k-step
   if (WL) {                                                         // the block's weights: issued with the first batch of loads
     if (a.w1 != nullptr) stage_weight<C, PW>(a.w1, 4 * C, sW1);
@@ -318,44 +375,45 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
     stage_weight<C, PW>(a.wv, C, sWv);
   }
   __syncthreads();
-  const int tok0 = 16 * wave;
+  const int tok0 = 16 * tt;
+  const int c0 = 16 * g;                  // first channel of the wave's first tile (tiles 16 G apart)
 
   // ---- projections: q from the query source, k / v from the key-value source (the same rows for self-attention)
-  if (tail) stage_ln_rows<C>(a, a.tail_res, a.lnq_g, a.lnq_b, b, wy, wx, sX, sPix, a.tail_raw, sTs,
-                             a.tail_rowscale != nullptr ? a.tail_rowscale[b] : 1.f, a.x_out);
-  else stage_ln_rows<C>(a, a.xq, a.lnq_g, a.lnq_b, b, wy, wx, sX, sPix);
+  if (tail) stage_ln_rows<C, NTHR>(a, a.tail_res, a.lnq_g, a.lnq_b, b, wy, wx, sX, sPix, a.tail_raw, sTs, sTs + TSP,
+                                   a.tail_rowscale != nullptr ? a.tail_rowscale[b] : 1.f, a.x_out);
+  else stage_ln_rows<C, NTHR>(a, a.xq, a.lnq_g, a.lnq_b, b, wy, wx, sX, sPix);
   __syncthreads();
   {
-    hrf_f4 acc[CT];
-    acc_bias<CT>(a.bq, 0, C, lane, acc);
-    if (WL) wave_gemm_l<C, PW, CT>(sWq, 0, C, sX + (tok0 + i) * PC, lane, acc);
-    else wave_gemm<C, CT>(a.wq, 0, C, sX, PC, tok0, lane, acc);
+    hrf_f4 acc[CTG];
+    acc_bias<CTG, G>(a.bq, c0, C, lane, acc);
+    if (WL) wave_gemm_l<C, PW, CTG>(sWq, 0, C, sX + (tok0 + i) * PC, lane, acc);
+    else wave_gemm<C, CTG, G>(a.wq, c0, C, sX, PC, tok0, lane, acc);
 #pragma unroll
-    for (int t = 0; t < CT; ++t)
+    for (int t = 0; t < CTG; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { const int n = 16 * t + 4 * q + r; if (n < C) sQ[(tok0 + i) * PC + n] = acc[t][r] * a.scale; }
+      for (int r = 0; r < 4; ++r) { const int n = c0 + 16 * G * t + 4 * q + r; if (n < C) sQ[(tok0 + i) * PC + n] = acc[t][r] * a.scale; }
   }
   if (a.xkv != a.xq) {                                               // (uniform) cross-attention: re-stage the tile
     __syncthreads();
-    stage_ln_rows<C>(a, a.xkv, a.lnkv_g, a.lnkv_b, b, wy, wx, sX, sPix);
+    stage_ln_rows<C, NTHR>(a, a.xkv, a.lnkv_g, a.lnkv_b, b, wy, wx, sX, sPix);
     __syncthreads();
   }
   {
-    hrf_f4 acc[CT];
-    acc_bias<CT>(a.bk, 0, C, lane, acc);
-    if (WL) wave_gemm_l<C, PW, CT>(sWk, 0, C, sX + (tok0 + i) * PC, lane, acc);
-    else wave_gemm<C, CT>(a.wk, 0, C, sX, PC, tok0, lane, acc);
+    hrf_f4 acc[CTG];
+    acc_bias<CTG, G>(a.bk, c0, C, lane, acc);
+    if (WL) wave_gemm_l<C, PW, CTG>(sWk, 0, C, sX + (tok0 + i) * PC, lane, acc);
+    else wave_gemm<C, CTG, G>(a.wk, c0, C, sX, PC, tok0, lane, acc);
 #pragma unroll
-    for (int t = 0; t < CT; ++t)
+    for (int t = 0; t < CTG; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { const int n = 16 * t + 4 * q + r; if (n < C) sK[(tok0 + i) * PC + n] = acc[t][r]; }
-    acc_bias<CT>(a.bv, 0, C, lane, acc);
-    if (WL) wave_gemm_l<C, PW, CT>(sWv, 0, C, sX + (tok0 + i) * PC, lane, acc);
-    else wave_gemm<C, CT>(a.wv, 0, C, sX, PC, tok0, lane, acc);
+      for (int r = 0; r < 4; ++r) { const int n = c0 + 16 * G * t + 4 * q + r; if (n < C) sK[(tok0 + i) * PC + n] = acc[t][r]; }
+    acc_bias<CTG, G>(a.bv, c0, C, lane, acc);
+    if (WL) wave_gemm_l<C, PW, CTG>(sWv, 0, C, sX + (tok0 + i) * PC, lane, acc);
+    else wave_gemm<C, CTG, G>(a.wv, c0, C, sX, PC, tok0, lane, acc);
 #pragma unroll
-    for (int t = 0; t < CT; ++t)
+    for (int t = 0; t < CTG; ++t)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) { const int n = 16 * t + 4 * q + r; if (n < C) sV[(tok0 + i) * PC + n] = acc[t][r]; }
+      for (int r = 0; r < 4; ++r) { const int n = c0 + 16 * G * t + 4 * q + r; if (n < C) sV[(tok0 + i) * PC + n] = acc[t][r]; }
   }
   __syncthreads();
 
@@ -365,7 +423,7 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
     const int qi = tok0 + i, qc = qi < NTOK ? qi : 0;
     const int yi = qc / 7, xi = qc - 7 * yi;
 #pragma unroll 1
-    for (int h = 0; h < HEADS; ++h) {
+    for (int h = g; h < HEADS; h += G) {
       hrf_f4 acc[4];
 #pragma unroll
       for (int t = 0; t < 4; ++t) acc[t] = hrf_f4{0.f, 0.f, 0.f, 0.f};
@@ -426,20 +484,21 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
   }
 
   // ---- out_proj + dropout / droppath + residual(s): x' leaves as 16-byte stores, and stays in the accumulators
-  HRF_WAVE_SYNC();                                                  // o rows were stored by other lanes of this wave
+  if (G == 1) HRF_WAVE_SYNC();                                      // o rows were stored by other lanes of this wave
+  else __syncthreads();                                             // ... and the other heads by the other waves of the token tile
   const int tok = tok0 + i;
   const int pix = sPix[tok];
   const long pc = pix >= 0 ? pix : 0;
-  hrf_f4 xo[CT];
-  acc_bias<CT>(a.bo, 0, C, lane, xo);
-  if (WL) wave_gemm_l<C, PW, CT>(sWo, 0, C, sQ + (tok0 + i) * PC, lane, xo);
-  else wave_gemm<C, CT>(a.wo, 0, C, sQ, PC, tok0, lane, xo);
+  hrf_f4 xo[CTG];
+  acc_bias<CTG, G>(a.bo, c0, C, lane, xo);
+  if (WL) wave_gemm_l<C, PW, CTG>(sWo, 0, C, sQ + (tok0 + i) * PC, lane, xo);
+  else wave_gemm<C, CTG, G>(a.wo, c0, C, sQ, PC, tok0, lane, xo);
   {
     const float rs = (a.rowscale != nullptr ? a.rowscale[pc / a.rows_per_sample] : 1.f) * a.mscale;
 #pragma unroll
-    for (int t = 0; t < CT; ++t) {
-      const int nb = 16 * t + 4 * q, nval = C - nb;
-      const bool nfull = 16 * (t + 1) <= C;
+    for (int t = 0; t < CTG; ++t) {
+      const int nb = c0 + 16 * G * t + 4 * q, nval = C - nb;
+      const bool nfull = c0 + 16 * (G * t + 1) <= C;
       const hrf_f4 r1 = ld_sel(nfull, a.res, pc * C + nb, nval);
       const hrf_f4 r2 = ld_sel(nfull, a.res2, pc * C + nb, a.res2 != nullptr ? nval : 0);
       const hrf_f4 mk = ld_sel(nfull, a.mask, pc * C + nb, a.mask != nullptr ? nval : 0);
@@ -461,59 +520,80 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
   }
   if (a.w1 == nullptr && a.out_rowstat == nullptr) return;          // (uniform)
 
-  // ---- LayerNorm statistics of the x' row (its C channels live in lanes j, j+16, j+32, j+48), two-pass as ln_stats
+  // ---- LayerNorm statistics of the x' row (its C channels live in lanes j, j+16, j+32, j+48), two-pass as ln_stats.
+  // G > 1: the row is spread over the G waves of the token tile - through the X tile (dead since the last projection), then
+  // every wave holds the whole row in the (t, r) order of the G = 1 form: the same sums, the same shuffles, the same bits
+  hrf_f4 xr[CT];
+  if (G == 1) {
+#pragma unroll
+    for (int t = 0; t < CT; ++t) xr[t] = xo[t < CTG ? t : 0];
+  } else {
+#pragma unroll
+    for (int t = 0; t < CTG; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) { const int n = c0 + 16 * G * t + 4 * q + r; if (n < C) sX[tok * PC + n] = xo[t][r]; }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < CT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xr[t][r] = ldz(sX + tok * PC, 16 * t + 4 * q + r, 16 * t + 4 * q + r < C);
+  }
   float sm = 0.f;
 #pragma unroll
   for (int t = 0; t < CT; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) sm += (16 * t + 4 * q + r < C) ? xo[t][r] : 0.f;
+    for (int r = 0; r < 4; ++r) sm += (16 * t + 4 * q + r < C) ? xr[t][r] : 0.f;
   sm += __shfl_xor(sm, 16); sm += __shfl_xor(sm, 32);
   const float mu = sm * (1.0f / (float)C);
   float sq = 0.f;
 #pragma unroll
   for (int t = 0; t < CT; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) { const float dd = (16 * t + 4 * q + r < C) ? xo[t][r] - mu : 0.f; sq = fmaf(dd, dd, sq); }
+    for (int r = 0; r < 4; ++r) { const float dd = (16 * t + 4 * q + r < C) ? xr[t][r] - mu : 0.f; sq = fmaf(dd, dd, sq); }
   sq += __shfl_xor(sq, 16); sq += __shfl_xor(sq, 32);
   const float rstd = hrf_rsqrt_nr(sq * (1.0f / (float)C) + a.out_eps);
-  if (a.out_rowstat != nullptr && q == 0 && pix >= 0) { a.out_rowstat[2 * pc] = mu; a.out_rowstat[2 * pc + 1] = rstd; }
+  if (a.out_rowstat != nullptr && q == 0 && g == 0 && pix >= 0) { a.out_rowstat[2 * pc] = mu; a.out_rowstat[2 * pc + 1] = rstd; }
   if (a.w1 == nullptr) return;                                      // (uniform)
 
-  // ---- CrossFFN head: h1 = LN_2(x') W1^T + b1 over the wave's own rows of the X tile, BatchNorm moments of h1
-  __syncthreads();                                                  // every wave is done with K / V (sStat aliases them)
+  // ---- CrossFFN head: h1 = LN_2(x') W1^T + b1 over the wave's own rows of the X tile (G > 1: the token tile's rows of the Q
+  // tile, written by its G waves), BatchNorm moments of h1
+  float* sL = G == 1 ? sX : sQ;
+  if (G == 1) __syncthreads();                                      // every wave is done with K / V (sStat aliases them)
 #pragma unroll
-  for (int t = 0; t < CT; ++t) {
-    const int nb = 16 * t + 4 * q;
-    const hrf_f4 g2 = ld_sel(16 * (t + 1) <= C, a.ln2_g, nb, C - nb), b2 = ld_sel(16 * (t + 1) <= C, a.ln2_b, nb, C - nb);
+  for (int t = 0; t < CTG; ++t) {
+    const int nb = c0 + 16 * G * t + 4 * q;
+    const bool nfull = c0 + 16 * (G * t + 1) <= C;
+    const hrf_f4 g2 = ld_sel(nfull, a.ln2_g, nb, C - nb), b2 = ld_sel(nfull, a.ln2_b, nb, C - nb);
 #pragma unroll
-    for (int r = 0; r < 4; ++r) if (nb + r < C) sX[tok * PC + nb + r] = fmaf((xo[t][r] - mu) * rstd, g2[r], b2[r]);
+    for (int r = 0; r < 4; ++r) if (nb + r < C) sL[tok * PC + nb + r] = fmaf((xo[t][r] - mu) * rstd, g2[r], b2[r]);
   }
-  HRF_WAVE_SYNC();                                                  // a token's row was stored by four lanes of this wave
-  constexpr int N1 = 4 * C, FT = (N1 / 16 >= 9) ? 9 : (N1 + 15) / 16;  // hidden width; 16-channel tiles per pass
+  if (G == 1) HRF_WAVE_SYNC();                                      // a token's row was stored by four lanes of this wave
+  else __syncthreads();                                             // ... of G waves (every wave left K / V two barriers ago)
+  constexpr int N1 = 4 * C, FT = ab_ffn_tiles(C, G);                // hidden width; 16-channel tiles per pass
   const bool tokv = pix >= 0;
 #pragma unroll 1
-  for (int n0 = 0; n0 < N1; n0 += 16 * FT) {
+  for (int n0 = c0; n0 < N1; n0 += 16 * G * FT) {
     hrf_f4 acc[FT];
-    acc_bias<FT>(a.b1, n0, N1, lane, acc);
+    acc_bias<FT, G>(a.b1, n0, N1, lane, acc);
     if (WL) wave_gemm_l<C, PW, FT>(sW1, n0, N1, sX + tok * PC, lane, acc);
-    else wave_gemm<C, FT>(a.w1, n0, N1, sX, PC, tok0, lane, acc);
+    else wave_gemm<C, FT, G>(a.w1, n0, N1, sL, PC, tok0, lane, acc);
 #pragma unroll
     for (int t = 0; t < FT; ++t) {
-      const int nb = n0 + 16 * t + 4 * q;
+      const int nb = n0 + 16 * G * t + 4 * q;
       if (tokv && nb < N1) hrf_st4(a.h1 + pc * N1 + nb, acc[t]);     // (4C is a multiple of 4: whole groups)
       if (a.stats1 != nullptr) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const float v = tokv ? acc[t][r] : 0.f;
           const float s1 = hrf_row16_sum(v), s2 = hrf_row16_sum(v * v);
-          if (i == 0 && nb + r < N1) { sStat[(wave * 2 + 0) * N1 + nb + r] = s1; sStat[(wave * 2 + 1) * N1 + nb + r] = s2; }
+          if (i == 0 && nb + r < N1) { sStat[(tt * 2 + 0) * N1 + nb + r] = s1; sStat[(tt * 2 + 1) * N1 + nb + r] = s2; }
         }
       }
     }
   }
   if (a.stats1 != nullptr) {
     __syncthreads();
-    for (int e = tid; e < 2 * N1; e += 256) {
+    for (int e = tid; e < 2 * N1; e += NTHR) {
       const int which = e / N1, ch = e - which * N1;
       const float s = (sStat[(0 * 2 + which) * N1 + ch] + sStat[(1 * 2 + which) * N1 + ch]) +
                       (sStat[(2 * 2 + which) * N1 + ch] + sStat[(3 * 2 + which) * N1 + ch]);
@@ -522,16 +602,16 @@ __global__ __launch_bounds__(256) void attn_block_fwd_kernel(HrfGroup<AbFwdArgs>
   }
 }
 
-template <int C, int HEADS>
+template <int C, int HEADS, int G>
 int launch_fwd(const hrf_attn_block_t& a0, const hrf_bn_fin_t& fin, int nwin, void* stream) {
   AbFwdArgs a;
   a.a = a0; a.fin = fin;
-  constexpr size_t smem = ((size_t)(C <= 36 ? 8 * C * ((C + 3) & ~3) : 0) + 4 * 64 * (C + 1) + 32 + HEADS * 176) * sizeof(float);
+  constexpr size_t smem = AbFwdLds<C, HEADS>::DYN;
 #ifndef HRF_EMUL
   static std::atomic<unsigned> lds_set{0u};
-  if (hrf_dyn_lds_once(lds_set, reinterpret_cast<const void*>(&attn_block_fwd_kernel<C, HEADS>), (int)smem) != HRF_OK) return HRF_ERR_LAUNCH;
+  if (hrf_dyn_lds_once(lds_set, reinterpret_cast<const void*>(&attn_block_fwd_kernel<C, HEADS, G>), (int)smem) != HRF_OK) return HRF_ERR_LAUNCH;
 #endif
-  return HRF_LAUNCH_G((attn_block_fwd_kernel<C, HEADS>), dim3(nwin), dim3(256), (unsigned)smem, stream, a);
+  return HRF_LAUNCH_G((attn_block_fwd_kernel<C, HEADS, G>), dim3(nwin), dim3(256 * G), (unsigned)smem, stream, a);
 }
 
 
@@ -1576,8 +1656,47 @@ __global__ __launch_bounds__(256) void fold_slots_kernel(const float* slots, con
 
 }  // namespace
 
+// widths of the forward kernel: head_dim 18 (HRFuser-T / HRFormer-T: 18/1, 36/2, 72/4, 144/8) and head_dim 39 (the B models:
+// 78/2, 156/4 - their 312/8 and 624/16 do not fit four LDS tiles)
 extern "C" int hrf_attn_block_supported(int C, int heads) {
-  return (heads > 0 && C == 18 * heads && (heads == 1 || heads == 2 || heads == 4 || heads == 8)) ? 1 : 0;
+  if (heads > 0 && C == 18 * heads && (heads == 1 || heads == 2 || heads == 4 || heads == 8)) return 1;
+  return (heads > 0 && C == 39 * heads && (heads == 2 || heads == 4)) ? 1 : 0;
+}
+
+// Wave-group form of the forward kernel per width: bit mask of the G it is built for, and the dispatcher's choice.
+// A G > 1 form is the default of a width only where its isolated median beat the G = 1 form of the parent build by more than that
+// build's min-max spread (tools/attn_fwd_groups_cost.py, profiles/attn_fwd_groups_cost.txt).
+static int g_ab_force_g = 0;              // hrf_debug_knob(36, g): 0 = the dispatcher's choice, 1 / 2 / 4 = that form
+static int ab_fwd_forms(int C) {
+  switch (C) {
+    case 72: case 144: return 1 | 4;
+    case 78: return 1 | 2;
+    case 156: return 1 | 2 | 4;
+    default: return 1;
+  }
+}
+static int ab_fwd_default_g(int C) {
+  // 78 / 156 (no parent kernel: against G = 1 of this build): G = 2 119.2 against 127.8 us on 644 windows and 118.8 against 142.2 us
+  // on 168 windows (G = 4 at 156: 118.9, no better than eight waves).  72 / 144 stay at G = 1: 43.0 against the parent's 43.4 us
+  // is less than what the SAME G = 1 source measures across the two builds (43.1), and 144 is slower (92.0 against 83.3 us) -
+  // four waves already occupy the four SIMDs of the CU and the kernel is bound by its fp32 MFMAs, which more waves do not add to
+  return (C == 78 || C == 156) ? 2 : 1;
+}
+// the form a launch of width C takes now, 0: a forced form this width is not built for
+static int ab_fwd_form(int C) {
+  const int gsel = g_ab_force_g != 0 ? g_ab_force_g : ab_fwd_default_g(C);
+  return (ab_fwd_forms(C) & gsel) != 0 ? gsel : 0;
+}
+// (reached through hrf_debug_knob only: not exported)  key 0 (knob 36): force a form; key 1 (knob 37): QUERY - returns the
+// form (1 / 2 / 4) a launch of width `value` takes now, 0 when the forced form is not built for it - not a status
+extern "C" __attribute__((visibility("hidden"))) int hrf_ab_knob(int key, int value) {
+  if (key == 0) {
+    if (value != 0 && value != 1 && value != 2 && value != 4) return HRF_ERR_ARG;
+    g_ab_force_g = value;
+    return HRF_OK;
+  }
+  if (key == 1) return ab_fwd_form(value);
+  return HRF_ERR_ARG;
 }
 
 extern "C" int hrf_attn_block_bwd_supported(int C, int heads) {
@@ -1661,14 +1780,24 @@ extern "C" int hrf_attn_block_fwd(const hrf_attn_block_t* p, void* stream) {
     } else if (a.tail_scale == nullptr || a.tail_shift == nullptr) return HRF_ERR_ARG;
   }
   a.tail_fin = nullptr;
+  const int form = ab_fwd_form(a.C);
+  if (form == 0) return HRF_ERR_ARG;                       // a forced wave-group form this width is not built for
   a.stats1 = hrf_det_tag(a.stats1);
   ab_geometry(a);
   const int nwin = a.B * a.nWh * a.nWw;
   if (nwin <= 0) return HRF_OK;
-  switch (a.heads) {
-    case 1: return launch_fwd<18, 1>(a, fin, nwin, stream);
-    case 2: return launch_fwd<36, 2>(a, fin, nwin, stream);
-    case 4: return launch_fwd<72, 4>(a, fin, nwin, stream);
-    default: return launch_fwd<144, 8>(a, fin, nwin, stream);
+  switch (a.C * 8 + form) {
+    case 18 * 8 + 1: return launch_fwd<18, 1, 1>(a, fin, nwin, stream);
+    case 36 * 8 + 1: return launch_fwd<36, 2, 1>(a, fin, nwin, stream);
+    case 72 * 8 + 1: return launch_fwd<72, 4, 1>(a, fin, nwin, stream);
+    case 72 * 8 + 4: return launch_fwd<72, 4, 4>(a, fin, nwin, stream);
+    case 144 * 8 + 1: return launch_fwd<144, 8, 1>(a, fin, nwin, stream);
+    case 144 * 8 + 4: return launch_fwd<144, 8, 4>(a, fin, nwin, stream);
+    case 78 * 8 + 1: return launch_fwd<78, 2, 1>(a, fin, nwin, stream);
+    case 78 * 8 + 2: return launch_fwd<78, 2, 2>(a, fin, nwin, stream);
+    case 156 * 8 + 1: return launch_fwd<156, 4, 1>(a, fin, nwin, stream);
+    case 156 * 8 + 2: return launch_fwd<156, 4, 2>(a, fin, nwin, stream);
+    case 156 * 8 + 4: return launch_fwd<156, 4, 4>(a, fin, nwin, stream);
+    default: return HRF_ERR_ARG;
   }
 }

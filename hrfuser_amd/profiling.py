@@ -95,7 +95,7 @@ def work_model(name, a):
         wts = 4.0 * (4 * C * C + (4 * C * C if ffn else 0))
         if name == 'hrf_attn_block_fwd':
             by = f4 * rows * C * (2 + 2 * cross + (4 if ffn else 0)) + wts
-            return f'attn_block_fwd_kernel<{C}, {heads}>', fwd, by
+            return f'attn_block_fwd_kernel<{C}, {heads}, {_lib.attn_fwd_form(C)}>', fwd, by     # (the wave-group form the dispatcher takes)
         slot = 4 * C * C + (4 * C * C if ffn else 0)
         by = f4 * (rows * C * (4 + 3 * cross + (8 if ffn else 0)) + nwin * (slot + heads * 49 * 49)) + wts
         return f'attn_block_bwd_kernel<{C}, {heads}>', 3.0 * fwd, by

@@ -1735,11 +1735,18 @@ def ffn_eval(ctx, x, ln, ffn):
 
 # ----------------------------------------------------------------------------- fused window-attention block
 _ATTN_FUSED = os.environ.get('HRF_ATTN_FUSED', '1') != '0'
+# head_dim 39 widths (HRFuser-B / HRFormer-B 78 / 156; forward-only kernels, so tape-free forwards only): OFF by default.  Measured on
+# MI355X (tools/attn_fwd_groups_cost.py, profiles/attn_fwd_groups_cost.txt): the eval forward of b_nus at 2 x 384 x 640 takes 6.80
+# ms/img [6.77-6.84] on the fused route against 6.48 [6.43-6.52] on the per-op chain - the launch is bound by its fp32 16x16x4 MFMAs
+# (119 us at 78 channels on 644 windows), the LDS-tiled row GEMMs of the chain are not.  HRF_ATTN_FUSED_D39=1 takes the launch.
+_ATTN_FUSED_D39 = os.environ.get('HRF_ATTN_FUSED_D39', '0') != '0'
 
 
 def attn_block_ok(ctx, C, heads):
     """Is the one-launch attention block (csrc/attn_block.hip) available for this width, in this mode?"""
     if not _ATTN_FUSED or not ctx.L.hrf_attn_block_supported(C, heads):
+        return False
+    if C == 39 * heads and not _ATTN_FUSED_D39:
         return False
     return (not ctx.record) or bool(ctx.L.hrf_attn_block_bwd_supported(C, heads))
 

@@ -228,7 +228,8 @@ int hrf_window_attn_bwd(const float* q, int ldq, int qoff, const float* k, int l
  * layers[0] :268) or of one modality of a fusion block (hrfuser_hrformer_based.py:305-317: norm1[k] / norm2[k] ->
  * MultiWindowCrossAttention :189-248 / WindowMCA :106-151 incl. Dropout -> DropPath + residuals; after the last modality
  * norm3 + the CrossFFN head) in ONE launch per direction, one workgroup per 7x7 window; head_dim 18 (HRFuser-T / STF
- * widths 18 / 36 / 72 / 144: hrf_attn_block_supported).  Rows are NHWC (B*H*W, C); weights keep the reference layouts
+ * widths 18 / 36 / 72 / 144) and, forward only, head_dim 39 (HRFuser-B / HRFormer-B widths 78 / 156; their 312 / 624 do
+ * not fit the LDS): hrf_attn_block_supported.  Rows are NHWC (B*H*W, C); weights keep the reference layouts
  * (Linear (out, in); for the packed qkv Linear pass three pointers into the same tensor).
  *   forward : out = res (+ res2) + mask*mscale*rowscale[b] * out_proj(attn(LN_q(xq), LN_kv(xkv)));  xkv == xq: self-
  *             attention (LN_kv unused).  mask / rowscale / res2 nullable; mscale = 1 when unused.
@@ -247,7 +248,8 @@ int hrf_window_attn_bwd(const float* q, int ldq, int qoff, const float* k, int l
  *             LN_q gamma / beta, LN_kv gamma / beta [C].  The relative-position-bias gradient is a leaf: the kernel leaves
  *             dS[key][query] of every (window, head) in ds_plane [windows][heads][49][49]; hrf_rpb_grad (any time later)
  *             gathers it into the replicated accumulator drpb [HRF_STAT_COPIES][169][heads] (copy_stride apart).
- *             hrf_attn_block_bwd_supported: widths 18 / 36.
+ *             hrf_attn_block_bwd_supported: widths 18 / 36 (72 / 144 / 78 / 156 are forward-only: a training step keeps
+ *             the per-op kernels there).
  * The last five fields are derived by the library.                                                                     */
 typedef struct hrf_attn_block {
   int B, H, W, C, heads;

@@ -10,7 +10,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REASONS = [
     (r'attn_block_bwd_kernel<18, 1, 4, true, true, false>', 'one 8-byte value stored in the prologue and reloaded once in the epilogue (cross + FFN variant: 3 launches per step)'),
-    (r'attn_block_fwd_kernel<144, 8>', '12x20 map: 12 windows for 256 CUs - one workgroup per CU whatever the registers; 9 channel tiles of accumulators per wave'),
+    (r'attn_block_fwd_kernel<144, 8, 1>', '12x20 map: 12 windows for 256 CUs - one workgroup per CU whatever the registers; 9 channel tiles of accumulators per wave'),
+    (r'attn_block_fwd_kernel<156, 4, 1>', 'HRFuser-B width, four-wave form: one workgroup per CU by its 160 KB of LDS; 10 channel tiles of accumulators per wave'),
     (r'wgrad3w_kernel', 'neck weight gradient (SURVEY 8f-1, not on the backbone step): 73.7 K accumulators per block in registers by design (36 MFMA tiles per wave); values spilled outside the pixel loop'),
     (r'lin_fwd_kernel<9, ', 'whole-row LayerNorm statistics of 144-channel rows at 12x20 (480 rows = 30 waves on the chip): occupancy is irrelevant, 9 channel tiles of accumulators per wave'),
 ]
