@@ -226,6 +226,10 @@ class Engine:
         for m in self.root.modules():
             hit = isinstance(m, nn.LayerNorm) or (isinstance(m, nn.Conv2d) and m.groups == m.in_channels and m.groups > 1)
             cand = (m.weight, m.bias) if hit else ()
+            if isinstance(m, CrossFFN) and m.layers[6].out_channels <= 48:
+                # fc3 of the narrow branches: its weight gradient comes from the row blocks of the data-gradient launch
+                # (hrf_conv_bwd_data_weight: hundreds of blocks per element at 96x160)
+                cand = (m.layers[6].weight, m.layers[6].bias)
             if hasattr(m, 'relative_position_bias_table'):        # window attention: dRPB + pad-key/value bias grads
                 cand = (m.relative_position_bias_table,) + tuple(
                     getattr(m, n).bias for n in ('qkv', 'k_proj', 'v_proj') if hasattr(m, n))

@@ -1059,6 +1059,45 @@ extern "C" int hrf_conv_bwd_data(const float* dy, int ldD, int doff, const float
   return hrf_check_launch();
 }
 
+// ---- data gradient + weight / bias gradient of a 1x1 convolution in ONE launch (lin_engine.hip, WG instantiations)
+extern "C" int hrf_conv_bwd_data_weight_supported(int Cin, int Cout, long rows, int epi, int bnb) {
+  if (Cin <= 0 || Cout <= 0 || rows <= 0 || (epi != 0 && epi != 1) || g_knob[4] != 0) return 0;
+  if (rows > (1L << 30)) return 0;
+  if (hrf_lin2_bwd_data_wide(rows, Cout, Cin)) return 0;       // the LDS-tiled route takes the shape: no fused form there
+  return hrf_lin_bwd_data_wg_ok((int)rows, Cout, Cin, bnb != 0) ? 1 : 0;
+}
+
+extern "C" int hrf_conv_bwd_data_weight(const float* dy, int ldD, int doff, const float* yraw,
+                                        const float* cA, const float* cB, const float* cC, const hrf_bn_bfin_t* bfin,
+                                        const float* w, int KH, int stride, int Cout,
+                                        int B, int H, int W, int Cin,
+                                        float* dx, int sB, int sY, int sX, int sC, int accumulate,
+                                        int epi, const float* xraw, int ldXr, const float* tf_scale,
+                                        const float* tf_shift, int act, double* stats,
+                                        const float* x, int ldX, float* dw, float* dbias, long copy_stride, void* stream) {
+  HRF_GROUP_CALL();
+  if (KH != 1 || stride != 1 || !(sC == 1 && sX == Cin && sY == W * sX && sB == H * sY)) return HRF_ERR_ARG;
+  if (bfin != nullptr && (cA == nullptr || bfin->C != Cout || Cout > HRF_FIN_MAXC || bfin->gstats == nullptr)) return HRF_ERR_ARG;
+  if (dy == nullptr || w == nullptr || dx == nullptr || dw == nullptr || copy_stride < 0) return HRF_ERR_ARG;
+  if (epi == 1 ? (xraw == nullptr || tf_scale == nullptr || tf_shift == nullptr || ldXr < Cin) : (x == nullptr || ldX < Cin)) return HRF_ERR_ARG;
+  const long rows = (long)B * H * W;
+  if (rows <= 0 || !hrf_conv_bwd_data_weight_supported(Cin, Cout, rows, epi, cA != nullptr ? 1 : 0)) return HRF_ERR_ARG;
+  if (!hrf_det_fin_ok(bfin)) return HRF_ERR_ARG;
+  bool det_ok = true;                                      // deterministic mode: the kernel adds into the shadow bins of dw / dbias
+  dw = hrf_det_grad(dw, det_ok); dbias = hrf_det_grad(dbias, det_ok);
+  if (!det_ok) return HRF_ERR_ARG;
+  LinBwdDataArgs l;
+  l.bfin = hrf_bn_bfin_t{};
+  if (bfin != nullptr) l.bfin = *bfin;
+  l.dy = dy; l.ldD = ldD; l.doff = doff; l.yraw = yraw; l.cA = cA; l.cB = cB; l.cC = cC; l.w = w;
+  l.dx = dx; l.ldDx = sX; l.accumulate = accumulate; l.epi = epi; l.xraw = xraw; l.ldXr = ldXr;
+  l.tf_scale = tf_scale; l.tf_shift = tf_shift; l.act = act; l.stats = hrf_det_tag(stats);
+  l.M = (int)rows; l.K = Cout; l.N = Cin;
+  l.x = x; l.ldX = ldX; l.dw = dw; l.dbias = dbias; l.copy_stride = copy_stride;
+  const int rc = hrf_lin_bwd_data_launch(l, stream);
+  return rc >= 0 ? rc : HRF_ERR_ARG;
+}
+
 // ---- the packed-weight front-end engine (conv3x_engine.hip)
 extern "C" int hrf_conv3x_supported(int Cin, int Cout, int KH, int stride, int dir) {
   if (KH != 3 || Cin <= 0 || Cout <= 0) return 0;

@@ -24,6 +24,11 @@ struct LinBwdDataArgs {
   double* stats;                                             // [HRF_STAT_COPIES][2*N] or null
   hrf_bn_bfin_t bfin;                                        // bfin.gstats != null: cA/cB/cC derived on load
   int M, K, N;
+  // dw != null (hrf_lin_bwd_data_launch only): the launch also adds the weight / bias gradient, dw[K][N] += dY'^T x.
+  // x rows [M][ldX] are read when epi != 1 (epi == 1: x = act(tf_scale * xraw + tf_shift)); dbias [K] nullable;
+  // copy_stride: element distance between the HRF_STAT_COPIES replicated accumulators (0: one copy)
+  const float* x = nullptr; int ldX = 0;
+  float* dw = nullptr; float* dbias = nullptr; long copy_stride = 0;
 };
 
 // Return HRF_OK after enqueueing the launch, or -1 when the shape is not supported (caller falls
@@ -31,10 +36,14 @@ struct LinBwdDataArgs {
 int hrf_lin_fwd_launch(const LinFwdArgs& a, void* stream);
 bool hrf_lin_fwd_emits_ln(const LinFwdArgs& a);       // true when the launch above covers whole rows per wave
 int hrf_lin_bwd_data_launch(const LinBwdDataArgs& a, void* stream);
+// the fused weight gradient (a.dw != null) is built for the contractions its call sites have: K <= 48 with a BatchNorm backward on
+// load (CrossFFN fc3 of the 18 / 36-channel branches), 48 < K <= 160 without (out_proj)
+bool hrf_lin_bwd_data_wg_ok(int M, int K, int N, bool bnb);
 // lin2_engine.hip: the same contract on an LDS-tiled data path, for wide problems (min(K, N) >= 64, M >= 1024); tried first
 int hrf_lin2_fwd_launch(const LinFwdArgs& a, void* stream);
 bool hrf_lin2_fwd_emits_ln(const LinFwdArgs& a);
 int hrf_lin2_bwd_data_launch(const LinBwdDataArgs& a, void* stream);
+bool hrf_lin2_bwd_data_wide(long M, int K, int N);    // the shape test of the launch above (it may still decline: 32-bit offsets)
 
 // ---- conv3_engine.hip: 3x3 / stride-1 / pad-1 convolution (forward and backward-data) on NHWC rows,
 // input halo tile staged ONCE per channel slab (no im2col re-reads), weights streamed through LDS.

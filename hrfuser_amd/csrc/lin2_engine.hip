@@ -697,6 +697,7 @@ int hrf_lin2_fwd_launch(const LinFwdArgs& a, void* stream) {
   }
 }
 bool hrf_lin2_fwd_emits_ln(const LinFwdArgs&) { return false; }
+bool hrf_lin2_bwd_data_wide(long M, int K, int N) { return wide_enough(M, K, N); }
 int hrf_lin2_bwd_data_launch(const LinBwdDataArgs& a, void* stream) {
   if (!wide_enough(a.M, a.K, a.N)) return -1;
   if (a.cA != nullptr && a.bfin.gstats != nullptr && a.K > HRF_FIN_MAXC) return -1;

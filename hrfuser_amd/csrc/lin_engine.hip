@@ -239,12 +239,23 @@ __global__ __launch_bounds__(256) void lin_fwd_kernel(HrfGroup<LinFwdArgs> grp) 
 }
 
 // --------------------------------------------------------------------------------- backward data
-template <int NT, bool BNB, int SB, bool SK, bool ONE = false>
+// WG: the launch ALSO accumulates the weight / bias gradient of the same 1x1 convolution, dW[k][ci] += sum_pix dY'[pix][k] *
+// x[pix][ci], from the operands the wave holds anyway: all of dY' of its 16 pixels (slab by slab, BatchNorm backward applied) and
+// the tile of the forward input for the channels it owns (epi == 1: act(tf_scale * xraw + tf_shift) of the raw tile the epilogue
+// needs; epi == 0: one extra row read).  Both fragments carry the pixel on the lane's ROW index; the contraction over pixels wants
+// it on the MFMA k axis, so each 16 x 16 tile passes through a wave-private LDS tile once (4 dword stores, one 16-byte load, no
+// block barrier).  dW is finished slab by slab (NT accumulator tiles): the four waves of a block meet in LDS (plain stores, one
+// adding pass, double-buffered: one barrier per slab) and the block adds to global memory in memory order; with SK the waves own
+// disjoint K slabs of ONE pixel tile and add on their own.  The data path is the code of WG = false.
+constexpr int LIN_WG_LD = 20;                               // row pitch of the transposition tile (16-byte rows, conflict-free stores)
+template <int NT, bool BNB, int SB, bool SK, bool ONE = false, bool WG = false>
 __global__ __launch_bounds__(256) void lin_bwd_data_kernel(HrfGroup<LinBwdDataArgs> grp) {
   const LinBwdDataArgs& a = grp.sel();
   __shared__ float sStat[4 * 2 * NT * 16];
   __shared__ __attribute__((aligned(16))) float sRed[SK ? 3 * NT * 256 : 4];
   __shared__ __attribute__((aligned(16))) float sFin[BNB ? 3 * HRF_FIN_MAXC : 4];
+  __shared__ __attribute__((aligned(16))) float sTr[WG ? 4 * 16 * LIN_WG_LD : 4];          // one transposition tile per wave
+  __shared__ __attribute__((aligned(16))) float sMrg[(WG && !SK) ? 2 * (4 * NT * 256 + 64) : 4];   // [buffer][wave][NT tiles | 16 bias sums]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, q = lane >> 4;
   const int n0w = blockIdx.y * (NT * 16);
@@ -271,6 +282,47 @@ __global__ __launch_bounds__(256) void lin_bwd_data_kernel(HrfGroup<LinBwdDataAr
     const bool nfull = n0w + 16 * (t + 1) <= a.N;
     xr[t] = ld_sel(nfull, a.xraw, pc * a.ldXr + chb, a.epi == 1 ? nval : 0);
     acc[t] = ld_sel(nfull, a.dx, pc * a.ldDx + chb, (a.epi != 1 && a.accumulate && (!SK || wave == 0)) ? nval : 0);
+  }
+
+  // WG: B fragments of the weight-gradient MFMAs - lane (j, q) holds x[pixel 4 q + m][channel n0w + 16 t + j], m = 0 .. 3
+  hrf_f4 xb[WG ? NT : 1];
+  float* const sT = sTr + (WG ? wave * 16 * LIN_WG_LD : 0);
+  const long wcp = WG ? (long)(blockIdx.x % HRF_STAT_COPIES) * a.copy_stride : 0;
+  int mbuf = 0;
+  if (WG) {
+    hrf_f4 xv[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      const int chb = n0w + 16 * t + 4 * q, nval = a.N - chb;
+      const bool nfull = n0w + 16 * (t + 1) <= a.N;
+      if (a.epi == 1) {
+        const hrf_f4 esc = ld_sel(nfull, a.tf_scale, chb, nval), esh = ld_sel(nfull, a.tf_shift, chb, nval);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xv[t][r] = fmaf(xr[t][r], esc[r], esh[r]);
+      } else {
+        xv[t] = ld_sel(nfull, a.x, pc * a.ldX + chb, nval);
+      }
+    }
+    if (a.epi == 1) {
+      hrf_with_act(a.act, [&](auto kind) HRF_KIND_INLINE {
+        constexpr int ACT = decltype(kind)::value;
+#pragma unroll
+        for (int t = 0; t < NT; ++t)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) xv[t][r] = hrf_act(ACT, xv[t][r]);
+      });
+    }
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const bool cv = n0w + 16 * t + 4 * q + r < a.N;
+        sT[(4 * q + r) * LIN_WG_LD + j] = (pixin && cv) ? xv[t][r] : 0.f;
+      }
+      HRF_WAVE_SYNC();
+      xb[t] = hrf_ld4(sT + j * LIN_WG_LD + 4 * q);
+      HRF_WAVE_SYNC();
+    }
   }
 
   const int nslab = (a.K + 15) >> 4;
@@ -304,6 +356,70 @@ __global__ __launch_bounds__(256) void lin_bwd_data_kernel(HrfGroup<LinBwdDataAr
         const float d = BNB ? fmaf(ca[s][r], dv[s][r], fmaf(cb[s][r], yv[s][r], cc[s][r])) : dv[s][r];
 #pragma unroll
         for (int t = 0; t < NT; ++t) acc[t] = hrf_mfma16(wv[s][t][r], d, acc[t]);
+      }
+    }
+    if (WG) {
+#pragma unroll
+      for (int s = 0; s < SB; ++s) {
+        const int slab = kb + s;
+        if (slab < k1) {                                       // (uniform per wave; without SK per block: the barrier below is safe)
+          float bs[4];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float d = BNB ? fmaf(ca[s][r], dv[s][r], fmaf(cb[s][r], yv[s][r], cc[s][r])) : dv[s][r];
+            const float dm = (pixin && 16 * slab + 4 * q + r < a.K) ? d : 0.f;
+            sT[(4 * q + r) * LIN_WG_LD + j] = dm;
+            bs[r] = hrf_row16_sum(dm);
+          }
+          HRF_WAVE_SYNC();
+          const hrf_f4 da = hrf_ld4(sT + j * LIN_WG_LD + 4 * q);   // A fragments: dY'[pixel 4 q + m][k = 16 slab + j]
+          HRF_WAVE_SYNC();
+          hrf_f4 wacc[NT];
+#pragma unroll
+          for (int t = 0; t < NT; ++t) wacc[t] = hrf_f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int t = 0; t < NT; ++t) wacc[t] = hrf_mfma16(da[m], xb[t][m], wacc[t]);
+          // lane (j, q), register r of tile t: dW[k = 16 slab + 4 q + r][ci = n0w + 16 t + j]
+          if (SK) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const int k = 16 * slab + 4 * q + r, ci = n0w + 16 * t + j;
+                if (k < a.K && ci < a.N) hrf_grad_add(a.dw, wcp, (long)k * a.N + ci, wacc[t][r]);
+              }
+            if (a.dbias != nullptr && blockIdx.y == 0 && j == 0) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (16 * slab + 4 * q + r < a.K) hrf_grad_add(a.dbias, wcp, 16 * slab + 4 * q + r, bs[r]);
+            }
+          } else {
+            float* const sM = sMrg + mbuf * (4 * NT * 256 + 64);
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+              for (int r = 0; r < 4; ++r) sM[wave * (NT * 256) + (t * 4 + r) * 64 + lane] = wacc[t][r];
+            if (j == 0) {
+#pragma unroll
+              for (int r = 0; r < 4; ++r) sM[4 * NT * 256 + wave * 16 + 4 * q + r] = bs[r];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+              const int idx = t * 256 + tid;
+              const float v = (sM[idx] + sM[NT * 256 + idx]) + (sM[2 * NT * 256 + idx] + sM[3 * NT * 256 + idx]);
+              const int k = 16 * slab + 4 * q + wave, ci = n0w + 16 * t + j;   // (tid = r * 64 + lane': r = wave, lane' = lane)
+              if (k < a.K && ci < a.N) hrf_grad_add(a.dw, wcp, (long)k * a.N + ci, v);
+            }
+            if (a.dbias != nullptr && blockIdx.y == 0 && tid < 16 && 16 * slab + tid < a.K) {
+              const float* b = sM + 4 * NT * 256;
+              hrf_grad_add(a.dbias, wcp, 16 * slab + tid, (b[tid] + b[16 + tid]) + (b[32 + tid] + b[48 + tid]));
+            }
+            mbuf ^= 1;                                         // (the next slab fills the other buffer: one barrier per slab)
+          }
+        }
       }
     }
   }
@@ -471,8 +587,42 @@ int hrf_lin_fwd_launch(const LinFwdArgs& a, void* stream) {
   }
 #define HRF_LB_V4(BNB_) { if (sk) { HRF_LB_NT(BNB_, true) } else { HRF_LB_NT(BNB_, false) } }
 
+// ---- the same launch with the fused weight gradient (lin_bwd_data_kernel<..., WG = true>): same plan, same grid
+#define HRF_LBW(NT_, BNB_, SB_, SK_, ONE_) HRF_LAUNCH_G((lin_bwd_data_kernel<NT_, BNB_, SB_, SK_, ONE_, true>), grid, dim3(256), 0, stream, a)
+#define HRF_LBW_ONE(NT_)                                           \
+  { if (a.K <= 16) { HRF_LBW(NT_, true, 1, false, true); }         \
+    else if (a.K <= 32) { HRF_LBW(NT_, true, 2, false, true); }    \
+    else { HRF_LBW(NT_, true, 3, false, true); } }
+#define HRF_LBW_WIDE(SK_) { if (a.K <= LIN_SB_WIDE_K) { HRF_LBW(5, false, LIN_SB, SK_, false); } else { HRF_LBW(5, false, LIN_SB_WIDE, SK_, false); } }
+#define HRF_LBW_NT(SK_)                                    \
+  switch (ntw) {                                           \
+    case 1: HRF_LBW(1, false, LIN_SB, SK_, false); break;  \
+    case 2: HRF_LBW(2, false, LIN_SB, SK_, false); break;  \
+    case 3: HRF_LBW(3, false, LIN_SB, SK_, false); break;  \
+    default: HRF_LBW_WIDE(SK_) break;                      \
+  }
+// (K <= 160: HRFuser-B's 312 / 624-channel out_proj gained nothing on MI355X - 41.71 against 41.68 ms per step - and the wide
+// 5-tile instantiation holds 237 VGPRs)
+constexpr int LIN_WG_MAX_K = 160;
+bool hrf_lin_bwd_data_wg_ok(int M, int K, int N, bool bnb) {
+  if (K < 4 || N < 4 || M <= 0 || K > LIN_WG_MAX_K) return false;
+  return K <= 48 ? bnb : !bnb;
+}
+static int lin_bwd_data_wg_launch(const LinBwdDataArgs& a, int ntw, bool sk, dim3 grid, void* stream) {
+  if (a.K <= 48) {
+    switch (ntw) {
+      case 1: HRF_LBW_ONE(1) break;
+      case 2: HRF_LBW_ONE(2) break;
+      case 3: HRF_LBW_ONE(3) break;
+      default: HRF_LBW_ONE(5) break;
+    }
+  } else if (sk) { HRF_LBW_NT(true) } else { HRF_LBW_NT(false) }
+  return hrf_check_launch();
+}
+
 int hrf_lin_bwd_data_launch(const LinBwdDataArgs& a, void* stream) {
   if (a.K < 4 || a.N < 4 || a.M <= 0) return -1;
+  if (a.dw != nullptr && !hrf_lin_bwd_data_wg_ok(a.M, a.K, a.N, a.cA != nullptr)) return -1;
   const int T = (a.N + 15) / 16;
   // (split K: only where the output is narrow - with >= 10 channel tiles a launch has blocks enough, and HRFuser-B's 1 248 -> 312 /
   // 2 496 -> 624 data gradients lost 0.4 ms per step to it)
@@ -483,6 +633,7 @@ int hrf_lin_bwd_data_launch(const LinBwdDataArgs& a, void* stream) {
   // (round 5: the cap holds for every variant - the 9-tile instantiations held 256 VGPRs + 71 ... 186 AGPRs, ONE wave per SIMD)
   if (ntw > LIN_BWD_EPI_MAX_NT) ntw = LIN_BWD_EPI_MAX_NT;
   const dim3 grid(hrf_cdiv(a.M, sk ? 16 : 64), hrf_cdiv(T, ntw));
+  if (a.dw != nullptr) return lin_bwd_data_wg_launch(a, ntw, sk, grid, stream);
   if (a.cA != nullptr) { HRF_LB_V4(true) } else { HRF_LB_V4(false) }
   return hrf_check_launch();
 }

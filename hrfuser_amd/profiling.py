@@ -52,6 +52,11 @@ def work_model(name, a):
         if a['KH'] == 1 and a['stride'] == 1 and a['sC'] == 1 and a['Cin'] >= 4 and a['Cout'] >= 4:
             return 'lin_bwd_data_kernel', fl, by
         return f"conv_bwd_data_kernel<{_pick_nt(a['Cin'])},{a['KH']},{int(a['cA'] is not None)}>", fl, by
+    if name == 'hrf_conv_bwd_data_weight':                 # 1x1, stride 1: the data gradient's traffic (+ the x rows when epi == 0,
+        M = a['B'] * a['H'] * a['W']                       # + dw), the FLOPs of both gradients
+        by = f4 * (M * a['Cout'] * (2 if a['cA'] is not None else 1) + 2 * a['Cin'] * a['Cout']
+                   + M * a['Cin'] * (2 if a['epi'] else 2 + bool(a['accumulate'])))
+        return 'lin_bwd_data_kernel', 4.0 * M * a['Cin'] * a['Cout'], by
     if name == 'hrf_conv_bwd_weight_s':
         Ho, Wo = _out_hw(a['H'], a['W'], a['KH'], a['stride'])
         Mp, Np = a['B'] * Ho * Wo, a['KH'] ** 2 * a['Cin']

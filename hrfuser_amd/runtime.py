@@ -351,7 +351,7 @@ class Strand:
 # their arguments as an array of up to HRF_GROUP_MAX problems, blockIdx.z selects the problem)
 _GROUPABLE = frozenset((
     'hrf_conv_fwd', 'hrf_conv_bwd_data', 'hrf_conv_fwd_packed', 'hrf_conv_bwd_data_packed', 'hrf_dwconv_fwd', 'hrf_dwconv_bwd_data',
-    'hrf_dwconv_bwd_data_weight',
+    'hrf_dwconv_bwd_data_weight', 'hrf_conv_bwd_data_weight',
     'hrf_attn_block_fwd', 'hrf_attn_block_bwd', 'hrf_affine_act_res', 'hrf_act_bwd', 'hrf_scale_add', 'hrf_ln_stats',
     'hrf_ln_bwd', 'hrf_window_attn_fwd', 'hrf_window_attn_bwd', 'hrf_fuse_sum', 'hrf_bilinear_up_bwd'))
 _NO_PARK = frozenset(_lib._RAW_RETURN) | frozenset((
@@ -956,6 +956,7 @@ class Ctx:
                                        'kernels would misread (set_deterministic between forward and backward)')
         if self.det:
             eng.det_begin()
+        self.lin_fused = lin_fused_sites()
         use_keep_list(self.owner._engine().keep)
         self.owner._engine().fs_prepare()
         # HRF_WGRAD=flush: every time all lanes are joined into the main lane and enough weight gradients are queued,
@@ -1345,6 +1346,34 @@ def _conv_out_hw(H, W, KH, stride):
     return (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KH) // stride + 1
 
 
+# HRF_LIN_FUSED_WG: weight / bias gradient of a 1x1 convolution from its data-gradient launch (hrf_conv_bwd_data_weight; csrc/
+# lin_engine.hip) instead of a launch of its own - `proj`: out_proj of the per-op transformer blocks (linear_residual), `ffn`:
+# CrossFFN fc3 of the narrow branches (_conv_backward, Lazy source), `all`, `0`.  Read when a backward pass starts (Ctx.
+# run_backward).  DESIGN 11 has the measurements behind the default.
+_LIN_FUSED_WG_DEFAULT = 'proj'
+# without replicated accumulators (Engine.grad_acc) every row block adds into the same dw element: ~25 ns per block and address
+_LIN_FUSED_MAX_ROWS_PLAIN = 2048
+
+
+def lin_fused_sites(value=None):
+    v = (os.environ.get('HRF_LIN_FUSED_WG', _LIN_FUSED_WG_DEFAULT) if value is None else value).strip().lower()
+    if v not in ('0', 'proj', 'ffn', 'all'):
+        raise ValueError(f"HRF_LIN_FUSED_WG={v!r}: one of 0, proj, ffn, all")
+    return {'0': frozenset(), 'proj': frozenset(('proj',)), 'ffn': frozenset(('ffn',)), 'all': frozenset(('proj', 'ffn'))}[v]
+
+
+def _lin_fused(ctx, site, Cin, Cout, rows, epi, bnb, copy_stride):
+    """Does this call site take the fused data + weight gradient launch now?"""
+    sites = ctx.__dict__.get('lin_fused')
+    if sites is None:
+        sites = lin_fused_sites()
+    if site not in sites or not hasattr(ctx.L, 'hrf_conv_bwd_data_weight'):
+        return False
+    if copy_stride == 0 and rows > _LIN_FUSED_MAX_ROWS_PLAIN:
+        return False
+    return bool(ctx.L.hrf_conv_bwd_data_weight_supported(Cin, Cout, rows, epi, 1 if bnb else 0))
+
+
 _S2F_MINPIX = int(os.environ.get('HRF_C3X_S2F_MINPIX', '4096'))   # A/B switch: stride-2 forward on the packed engine from this many output pixels
 _IM2COL = os.environ.get('HRF_IM2COL', '1') != '0'      # A/B switch: the stem's first convolution through hrf_im2col3x3
 
@@ -1390,6 +1419,17 @@ def _conv_backward(ctx, src, weight, bias, KH, stride, Cout, dy, ldD, doff, yraw
     elif isinstance(src, Lazy):
         ps = src.st
         ps.du = _new_like(ps.raw)
+        fused = False
+        if KH == 1 and stride == 1 and weight.requires_grad and tuple(strides) == _nhwc_strides(B, H, W, Cin):
+            eng = ctx.owner._engine()
+            wacc, cs = eng.grad_acc(weight)
+            bacc, bcs = eng.grad_acc(bias) if (bias is not None and bias.requires_grad) else (None, cs)
+            fused = bcs == cs and _lin_fused(ctx, 'ffn', Cin, Cout, B * H * W, 1, cA is not None, cs)
+        if fused:                                 # weight / bias gradient from the same pass (no leaf launch)
+            L.hrf_conv_bwd_data_weight(dy, ldD, doff, yraw, cA, cB, cC, bfin, weight, KH, stride, Cout, B, H, W, Cin,
+                                       ps.du, *strides, 0, 1, ps.raw, Cin, ps.scale, ps.shift, _TF2ACT[src.mode],
+                                       ps.gstats, None, 0, wacc, bacc, cs, s)
+            return
         bwd_data(dy, ldD, doff, yraw, cA, cB, cC, bfin, weight, KH, stride, Cout, B, H, W, Cin,
                             ps.du, *strides, 0, 1, ps.raw, Cin, ps.scale, ps.shift, _TF2ACT[src.mode],
                             ps.gstats, s)
@@ -1630,12 +1670,17 @@ def linear_residual(ctx, o, lin, res, res2=None, drop=None):
             mask, mscale, rowscale = drop
             dy = _new_like(g)
             L.hrf_scale_add(g, mask, mscale, rowscale, H * W, None, None, dy, rows, C, s)
-        if w.requires_grad:
-            L.hrf_conv_bwd_weight(dy, C, 0, None, None, None, None, o.t, *strides, B, H, W, C, 1, 1, C,
-                                  TF_NONE, None, None, None, w.grad, b.grad if b is not None else None, s)
         og, acc = o.grad_target()
-        L.hrf_conv_bwd_data(dy, C, 0, None, None, None, None, None, w, 1, 1, C, B, H, W, C, og, *strides, acc,
-                            0, None, 0, None, None, 0, None, s)
+        if w.requires_grad and _lin_fused(ctx, 'proj', C, C, rows, 0, False, 0):
+            # dW / db from the data-gradient launch: the operand rows are in its registers anyway (no launch of its own on the lane)
+            L.hrf_conv_bwd_data_weight(dy, C, 0, None, None, None, None, None, w, 1, 1, C, B, H, W, C, og, *strides, acc,
+                                       0, None, 0, None, None, 0, None, o.t, C, w.grad, b.grad if b is not None else None, 0, s)
+        else:
+            if w.requires_grad:
+                L.hrf_conv_bwd_weight(dy, C, 0, None, None, None, None, o.t, *strides, B, H, W, C, 1, 1, C,
+                                      TF_NONE, None, None, None, w.grad, b.grad if b is not None else None, s)
+            L.hrf_conv_bwd_data(dy, C, 0, None, None, None, None, None, w, 1, 1, C, B, H, W, C, og, *strides, acc,
+                                0, None, 0, None, None, 0, None, s)
         # identity paths: the residual streams receive the output gradient unchanged
         if res2 is not None and res2.needs_grad:
             if res2.grad is None and res.grad is None and res.needs_grad:

@@ -117,6 +117,27 @@ int hrf_conv_bwd_data(const float* dy, int ldD, int doff, const float* yraw,
                       float* dx, int sB, int sY, int sX, int sC, int accumulate,
                       int epi, const float* xraw, int ldXr, const float* tf_scale,
                       const float* tf_shift, int act, double* stats, void* stream);
+/* hrf_conv_bwd_data (same arguments, the same dx / `stats` moments / bfin publication, bit for bit) that ALSO accumulates the
+ * weight / bias gradient of the same convolution - dw[Cout][Cin] +=, dbias[Cout] += (nullable), what hrf_conv_bwd_weight adds
+ * for these operands - from the rows the data-gradient kernel holds in registers anyway: no second pass over dy, no leaf launch.
+ * The forward input of the convolution is `x` rows ([B*H*W][ldX], read when epi == 0) or, with epi == 1,
+ * act(tf_scale * xraw + tf_shift) of the rows the epilogue reads.  dw / dbias: fp32 atomics (zero or pre-load the targets);
+ * copy_stride > 0: [HRF_STAT_COPIES] replicated accumulators that far apart (see above; for launches of many row blocks),
+ * folded by hrf_fold_copies; 0: plain accumulation.  Deterministic mode: registered accumulators, as hrf_conv_bwd_weight.
+ * Taken for KH = 1, stride 1, dense NHWC rows (sC = 1, sX = Cin, sY = W*sX, sB = H*sY) on the register-only row-GEMM route when
+ * hrf_conv_bwd_data_weight_supported(Cin, Cout, rows = B*H*W, epi, bnb = (cA != NULL)) says 1 (a query: launches nothing) -
+ * Cout <= 48 with a BatchNorm backward on load (CrossFFN fc3 of narrow branches), 48 < Cout <= 160 without one (out_proj),
+ * and a shape the LDS-tiled route of hrf_conv_bwd_data does not claim.  Every other call returns HRF_ERR_ARG before anything is
+ * launched or written: the caller issues hrf_conv_bwd_data and hrf_conv_bwd_weight. */
+int hrf_conv_bwd_data_weight_supported(int Cin, int Cout, long rows, int epi, int bnb);
+int hrf_conv_bwd_data_weight(const float* dy, int ldD, int doff, const float* yraw,
+                             const float* cA, const float* cB, const float* cC, const hrf_bn_bfin_t* bfin,
+                             const float* w, int KH, int stride, int Cout,
+                             int B, int H, int W, int Cin,
+                             float* dx, int sB, int sY, int sX, int sC, int accumulate,
+                             int epi, const float* xraw, int ldXr, const float* tf_scale,
+                             const float* tf_shift, int act, double* stats,
+                             const float* x, int ldX, float* dw, float* dbias, long copy_stride, void* stream);
 /* dW += , dbias += (split-K over pixels, fp32 atomics: zero or pre-load the targets).          */
 int hrf_conv_bwd_weight(const float* dy, int ldD, int doff, const float* yraw,
                         const float* cA, const float* cB, const float* cC,
