@@ -717,6 +717,9 @@ class LocalWindowSelfAttention(nn.Module):
         a = self.attn
         B, H, W, C = x.t.shape
         lin = R.ln_input(ctx, x, ln, cache)
+        if R.attn_proj_ok(ctx, C, a.num_heads):        # LayerNorm + qkv + the attention core: one launch per (window, head)
+            o = R.window_attention_proj(ctx, lin, lin, (a.qkv,), a.relative_position_bias_table, a.num_heads)
+            return R.linear_residual(ctx, o, a.out_proj, x, drop=drop)
         qkv = R.Plain(R._new((B * H * W, 3 * C), x.t.device))
         R.linear_into(ctx, lin, a.qkv, qkv, 0)
         bq = a.qkv.bias
@@ -826,13 +829,17 @@ class MultiWindowCrossAttention(nn.Module):
         a = self.attn
         B, H, W, C = acc.t.shape
         dev = acc.t.device
-        q = R.Plain(R._new((B * H * W, C), dev))
-        kv = R.Plain(R._new((B * H * W, 2 * C), dev))
-        R.linear_into(ctx, q_in, a.q_proj, q, 0)
-        R.linear_into(ctx, kv_in, a.k_proj, kv, 0)
-        R.linear_into(ctx, kv_in, a.v_proj, kv, C)
-        o = R.window_attention(ctx, q, 0, kv, 0, kv, C, a.k_proj.bias, a.v_proj.bias, a.k_proj.bias, 0,
-                               a.v_proj.bias, 0, a.relative_position_bias_table, a.num_heads, (B, H, W, C))
+        if R.attn_proj_ok(ctx, C, a.num_heads):        # both LayerNorms + q / k / v + the attention core: one launch per (window, head)
+            o = R.window_attention_proj(ctx, q_in, kv_in, (a.q_proj, a.k_proj, a.v_proj), a.relative_position_bias_table,
+                                        a.num_heads)
+        else:
+            q = R.Plain(R._new((B * H * W, C), dev))
+            kv = R.Plain(R._new((B * H * W, 2 * C), dev))
+            R.linear_into(ctx, q_in, a.q_proj, q, 0)
+            R.linear_into(ctx, kv_in, a.k_proj, kv, 0)
+            R.linear_into(ctx, kv_in, a.v_proj, kv, C)
+            o = R.window_attention(ctx, q, 0, kv, 0, kv, C, a.k_proj.bias, a.v_proj.bias, a.k_proj.bias, 0,
+                                   a.v_proj.bias, 0, a.relative_position_bias_table, a.num_heads, (B, H, W, C))
         drop = None
         p = a.proj_drop.p
         if ctx.training and a.proj_drop.training and (p > 0 or drop_path_scale is not None):

@@ -12,6 +12,7 @@
 //
 // Mapping: one 256-thread block per (window, head); all contractions run on v_mfma_f32_16x16x4_f32 with the 49 tokens
 // padded to 64 (attn_fwd_mfma_kernel / attn_bwd_mfma_kernel below).
+// attn_proj_fwd_kernel is the forward with LayerNorm and the head's q / k / v projections inside the same block.
 #include "hrf_common.h"
 #include "hrf_group.h"
 #include "../../include/hrfuser_hip.h"
@@ -96,24 +97,15 @@ __device__ __forceinline__ void stage_tiles(const AttnArgs& a, int b, int wy, in
 // wave shuffles (xor 16, 32), and the probabilities already sit in the A-operand position of the second contraction
 // (contraction slot q of MFMA (t, r) <-> key 16t + 4q + r), so P never moves: O = P V is 16 x ceil(D/16) MFMAs whose B
 // operand is a V row read from LDS.  K/V/Q tiles are staged once per block (pitch 16*ceil(D/16) + 1).
+// The core proper, shared by the two forward kernels: score tiles, relative position bias, softmax and P V of the wave's 16
+// queries from staged [64][P] tiles (sQ scaled; zero outside the 49 x D payload) and the head's bias table sT, then the
+// store of the real tokens' output rows.  The caller has staged and synchronised.
 template <int D>
-__global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(HrfGroup<AttnArgs> grp) {
-  const AttnArgs& a = grp.sel();
+__device__ __forceinline__ void attn_core_fwd(const AttnArgs& a, int b, int wy, int wx, int h, const float* sQ, const float* sK,
+                                              const float* sV, const float* sT, int wave, int i, int q) {
   constexpr int KS = (D + 3) / 4;             // contraction steps of Q K^T
   constexpr int DT = (D + 15) / 16;           // 16-wide output tiles of P V
   constexpr int P = DT * 16 + 1;              // LDS pitch (floats)
-  __shared__ float sQ[64 * P];
-  __shared__ float sK[64 * P];
-  __shared__ float sV[64 * P];
-  __shared__ float sT[176];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = blockIdx.y;
-  const int i = lane & 15, q = lane >> 4;
-  const int win = blockIdx.x;
-  const int wx = win % a.nWw, wy = (win / a.nWw) % a.nWh, b = win / (a.nWw * a.nWh);
-  stage_tiles<D, P, false>(a, b, wy, wx, h, sQ, sK, sV, nullptr);
-  for (int e = threadIdx.x; e < 169; e += 256) sT[e] = a.rpb[e * a.heads + h];
-  __syncthreads();
-
   // ---- S^T tiles: acc[t][r] = S[query 16w + i][key 16t + 4q + r]
   hrf_f4 acc[4];
 #pragma unroll
@@ -183,6 +175,155 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(HrfGroup<AttnArgs> g
       if (px >= 0 && d < D) a.o[(long)px * a.ldo + h * D + d] = o[dt][r] * invr;
     }
   }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(HrfGroup<AttnArgs> grp) {
+  const AttnArgs& a = grp.sel();
+  constexpr int DT = (D + 15) / 16;           // 16-wide output tiles of P V
+  constexpr int P = DT * 16 + 1;              // LDS pitch (floats)
+  __shared__ float sQ[64 * P];
+  __shared__ float sK[64 * P];
+  __shared__ float sV[64 * P];
+  __shared__ float sT[176];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = blockIdx.y;
+  const int i = lane & 15, q = lane >> 4;
+  const int win = blockIdx.x;
+  const int wx = win % a.nWw, wy = (win / a.nWw) % a.nWh, b = win / (a.nWw * a.nWh);
+  stage_tiles<D, P, false>(a, b, wy, wx, h, sQ, sK, sV, nullptr);
+  for (int e = threadIdx.x; e < 169; e += 256) sT[e] = a.rpb[e * a.heads + h];
+  __syncthreads();
+  attn_core_fwd<D>(a, b, wy, wx, h, sQ, sK, sV, sT, wave, i, q);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Per-(window, head) forward with LayerNorm and the q / k / v projections IN the kernel (hrf_window_attn_proj_fwd): what the
+// chain runs as hrf_conv_fwd(TF_LN) -> [rows][3C] buffer -> attn_fwd_mfma_kernel is one launch of windows x heads blocks.  A
+// block stages x^ = LayerNorm(x) of its window's 49 rows (row statistics are an input, the loader arithmetic is the row-GEMM
+// engines': fmaf((x - mean) * rstd, gamma, beta)), projects ITS head's D rows of wq / wk / wv on the MFMA pipe straight into the
+// core's sQ / sK / sV tiles and runs attn_core_fwd.  A padded token's x^ row is zero, so its key / value is the projection bias -
+// what kpad / vpad synthesise for the chain; rows 49 .. 63 and columns D .. 16 DT - 1 of the tiles are zeros.
+struct AttnProjArgs {
+  AttnArgs c;                                 // geometry, heads, scale, rpb, o / ldo (the q / k / v fields are unused)
+  int C;
+  const float* xq; const float* xkv;          // [rows][C]; xkv == xq: self-attention
+  const float* lnq_g; const float* lnq_b; const float* lnkv_g; const float* lnkv_b;
+  const float* statq; const float* statkv;    // [rows][2] (mean, rstd)
+  const float* wq; const float* bq; const float* wk; const float* bk; const float* wv; const float* bv;
+  float* sq; int ldsq, sqoff;                 // optional stores of the UNscaled q and of k / v, real tokens only
+  float* sk; int ldsk, skoff;
+  float* sv; int ldsv, svoff;
+};
+
+// x^ tile [64][XP], XP = 4 ceil(C / 4) + 1 (odd; C + 1 where C is a multiple of 4): zero outside the 49 x C payload and in the rows of
+// padded tokens.  The global loads go out in batches of 8 elements per thread ahead of their LDS stores.
+__device__ __forceinline__ void stage_xhat(const AttnArgs& g, int b, int wy, int wx, const float* x, const float* stat,
+                                           const float* gam, const float* bet, int C, int XP, float* sX, bool zero) {
+  if (zero) {
+    for (int e = threadIdx.x; e < 64 * XP; e += 256) {
+      const int j = e / XP, c = e - j * XP;
+      if (j >= NT || c >= C) sX[e] = 0.f;
+    }
+  }
+  constexpr int U = 8;
+  const int n = NT * C;
+  for (int e0 = threadIdx.x; e0 < n; e0 += 256 * U) {
+    float xv[U];
+    int dst[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = e0 + 256 * u;
+      const int ec = e < n ? e : 0;
+      const int j = ec / C, c = ec - j * C;
+      const int pix = tok_pixel(g, b, wy, wx, j);
+      const long pc = pix >= 0 ? pix : 0;         // unconditional clamped loads, select afterwards
+      const float x0 = x[pc * C + c], mean = stat[2 * pc], rstd = stat[2 * pc + 1];
+      const float v = fmaf((x0 - mean) * rstd, gam[c], bet[c]);
+      xv[u] = pix >= 0 ? v : 0.f;
+      dst[u] = e < n ? j * XP + c : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (dst[u] >= 0) sX[dst[u]] = xv[u];
+  }
+}
+
+// dst tile rows 16w .. 16w+15 of wave w = (x^ W_h^T + bias_h) * mul: weight rows h D + 16 dt + i are the row operand (read from
+// global memory: each element is used once per wave), the wave's 16 x^ rows the column operand - lane (i, q) ends up with
+// token 16w + i, outputs 16 dt + 4q + r.  gdst != null: the unscaled rows of real tokens also go to gdst[pix][goff + h D + d].
+template <int D>
+__device__ __forceinline__ void project_head(const float* sX, int XP, int C, const float* w, const float* bias, int h, float mul,
+                                             float* sDst, float* gdst, int gld, int goff, int pix) {
+  constexpr int DT = (D + 15) / 16, P = DT * 16 + 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int i = lane & 15, q = lane >> 4;
+  const int tok = 16 * wave + i;
+  hrf_f4 acc[DT];
+  const float* wrow[DT];
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt) {
+    acc[dt] = hrf_f4{0.f, 0.f, 0.f, 0.f};
+    const int row = 16 * dt + i;
+    wrow[dt] = w + (long)(h * D + (row < D ? row : 0)) * C;
+  }
+  const float* xrow = sX + tok * XP + q;
+  const int KS = (C + 3) / 4;
+#pragma unroll 4
+  for (int kk = 0; kk < KS; ++kk) {
+    const int c = 4 * kk + q;
+    const bool cok = c < C;                     // (false in the last step of a width that is no multiple of 4 only)
+    const int cc = cok ? c : 0;
+    const float xv = xrow[4 * kk];
+#pragma unroll
+    for (int dt = 0; dt < DT; ++dt) {
+      const float w0 = wrow[dt][cc];
+      acc[dt] = hrf_mfma16((cok && 16 * dt + i < D) ? w0 : 0.f, xv, acc[dt]);
+    }
+  }
+#pragma unroll
+  for (int dt = 0; dt < DT; ++dt)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int d = 16 * dt + 4 * q + r;
+      const int col = h * D + (d < D ? d : 0);
+      const float val = acc[dt][r] + (bias != nullptr ? bias[col] : 0.f);
+      const bool live = d < D && tok < NT;
+      sDst[tok * P + d] = live ? val * mul : 0.f;
+      if (gdst != nullptr && live && pix >= 0) gdst[(long)pix * gld + goff + col] = val;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(256) void attn_proj_fwd_kernel(HrfGroup<AttnProjArgs> grp) {
+  const AttnProjArgs& a = grp.sel();
+  const AttnArgs& g = a.c;
+  constexpr int DT = (D + 15) / 16, P = DT * 16 + 1;
+  HRF_DYN_SMEM(float, smem);
+  float* sQ = smem;
+  float* sK = sQ + 64 * P;
+  float* sV = sK + 64 * P;
+  float* sT = sV + 64 * P;                    // [176]
+  float* sX = sT + 176;                       // [64][XP]
+  const int C = a.C, XP = 4 * ((C + 3) / 4) + 1;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = blockIdx.y;
+  const int win = blockIdx.x;
+  const int wx = win % g.nWw, wy = (win / g.nWw) % g.nWh, b = win / (g.nWw * g.nWh);
+  const int tok = 16 * wave + (lane & 15);
+  const int pix = tok < NT ? tok_pixel(g, b, wy, wx, tok) : -1;
+  const bool cross = a.xkv != a.xq;           // (uniform)
+  stage_xhat(g, b, wy, wx, a.xq, a.statq, a.lnq_g, a.lnq_b, C, XP, sX, true);
+  for (int e = threadIdx.x; e < 169; e += 256) sT[e] = g.rpb[e * g.heads + h];
+  __syncthreads();
+  project_head<D>(sX, XP, C, a.wq, a.bq, h, g.scale, sQ, a.sq, a.ldsq, a.sqoff, pix);
+  if (cross) {
+    __syncthreads();                          // every wave is done with the query rows
+    stage_xhat(g, b, wy, wx, a.xkv, a.statkv, a.lnkv_g, a.lnkv_b, C, XP, sX, false);
+    __syncthreads();
+  }
+  project_head<D>(sX, XP, C, a.wk, a.bk, h, 1.0f, sK, a.sk, a.ldsk, a.skoff, pix);
+  project_head<D>(sX, XP, C, a.wv, a.bv, h, 1.0f, sV, a.sv, a.ldsv, a.svoff, pix);
+  __syncthreads();
+  attn_core_fwd<D>(g, b, wy, wx, h, sQ, sK, sV, sT, wave, lane & 15, lane >> 4);
 }
 
 // MFMA backward.  Every 49x49 quantity is produced twice, once per orientation, because an MFMA result can feed the
@@ -479,4 +620,49 @@ extern "C" int hrf_window_attn_bwd(const float* q, int ldq, int qoff, const floa
   if (nwin <= 0) return HRF_OK;
   HRF_ATTN_DISPATCH(attn_bwd_mfma_kernel)
   return hrf_check_launch();
+}
+
+extern "C" int hrf_window_attn_proj_supported(int C, int heads) {
+  if (heads <= 0 || C <= 0 || C % heads || C > 160) return 0;
+  const int D = C / heads;
+  return (D == 18 || D == 39) ? 1 : 0;
+}
+
+template <int D>
+static int launch_attn_proj(const AttnProjArgs& a, int nwin, void* stream) {
+  constexpr int P = ((D + 15) / 16) * 16 + 1;
+  const size_t smem = ((size_t)192 * P + 176 + (size_t)64 * (4 * ((a.C + 3) / 4) + 1)) * sizeof(float);
+#ifndef HRF_EMUL
+  constexpr size_t smem_max = ((size_t)192 * P + 176 + (size_t)64 * 161) * sizeof(float);     // C <= 160
+  static std::atomic<unsigned> lds_set{0u};
+  if (hrf_dyn_lds_once(lds_set, reinterpret_cast<const void*>(&attn_proj_fwd_kernel<D>), (int)smem_max) != HRF_OK) return HRF_ERR_LAUNCH;
+#endif
+  return HRF_LAUNCH_G((attn_proj_fwd_kernel<D>), dim3(nwin, a.c.heads), dim3(256), (unsigned)smem, stream, a);
+}
+
+extern "C" int hrf_window_attn_proj_fwd(const hrf_attn_proj_t* p, void* stream) {
+  HRF_GROUP_CALL();
+  if (p == nullptr || p->B <= 0 || p->H <= 0 || p->W <= 0 || !hrf_window_attn_proj_supported(p->C, p->heads)) return HRF_ERR_ARG;
+  if (p->xq == nullptr || p->xkv == nullptr || p->lnq_g == nullptr || p->lnq_b == nullptr || p->rowstat_q == nullptr ||
+      p->wq == nullptr || p->wk == nullptr || p->wv == nullptr || p->rpb == nullptr || p->o == nullptr || p->ldo < p->C)
+    return HRF_ERR_ARG;
+  if (p->xkv != p->xq && (p->lnkv_g == nullptr || p->lnkv_b == nullptr || p->rowstat_kv == nullptr)) return HRF_ERR_ARG;
+  if ((p->q_out != nullptr && (p->qoff < 0 || p->ldq < p->qoff + p->C)) || (p->k_out != nullptr && (p->koff < 0 || p->ldk < p->koff + p->C)) ||
+      (p->v_out != nullptr && (p->voff < 0 || p->ldv < p->voff + p->C)))
+    return HRF_ERR_ARG;
+  const int D = p->C / p->heads;
+  AttnProjArgs a{};
+  a.c.rpb = p->rpb; a.c.o = p->o; a.c.ldo = p->ldo; a.c.B = p->B; a.c.H = p->H; a.c.W = p->W; a.c.heads = p->heads;
+  a.c.scale = 1.0f / sqrtf((float)D);
+  window_geom(a.c);
+  a.C = p->C; a.xq = p->xq; a.xkv = p->xkv;
+  a.lnq_g = p->lnq_g; a.lnq_b = p->lnq_b; a.lnkv_g = p->lnkv_g; a.lnkv_b = p->lnkv_b;
+  a.statq = p->rowstat_q; a.statkv = p->rowstat_kv;
+  a.wq = p->wq; a.bq = p->bq; a.wk = p->wk; a.bk = p->bk; a.wv = p->wv; a.bv = p->bv;
+  a.sq = p->q_out; a.ldsq = p->ldq; a.sqoff = p->qoff;
+  a.sk = p->k_out; a.ldsk = p->ldk; a.skoff = p->koff;
+  a.sv = p->v_out; a.ldsv = p->ldv; a.svoff = p->voff;
+  const int nwin = p->B * a.c.nWh * a.c.nWw;
+  const int rc = D == 18 ? launch_attn_proj<18>(a, nwin, stream) : launch_attn_proj<39>(a, nwin, stream);
+  return rc != HRF_OK ? rc : hrf_check_launch();
 }

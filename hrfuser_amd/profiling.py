@@ -90,6 +90,13 @@ def work_model(name, a):
         if name == 'hrf_window_attn_fwd':
             return f"attn_fwd_kernel<{D}>", 2 * unit, f4 * P * a['C'] * 4
         return f"attn_bwd_kernel<{D}>", 5 * unit, f4 * P * a['C'] * 7
+    if name == 'hrf_window_attn_proj_fwd':             # LayerNorm on load + the head's q / k / v projections + the attention core
+        C, heads = a['C'], a['heads']
+        rows = float(a['B']) * a['H'] * a['W']
+        nwin = a['B'] * math.ceil(a['H'] / 7) * math.ceil(a['W'] / 7)
+        fl = 2.0 * rows * C * C * 3 + 2 * 2.0 * 49 * 49 * (C // heads) * nwin * heads
+        by = f4 * (rows * C * (2 + bool(a.get('cross')) + 3 * bool(a.get('store'))) + 3 * C * C)
+        return f'attn_proj_fwd_kernel<{C // heads}>', fl, by
     if name in ('hrf_attn_block_fwd', 'hrf_attn_block_bwd'):
         C, heads = a['C'], a['heads']
         rows = float(a['B']) * a['H'] * a['W']
@@ -162,9 +169,12 @@ class ProfLib:
                     v = getattr(p, f)
                     if f in ('B', 'H', 'W', 'C', 'heads', 'hidden'):
                         d[f] = v
-                if hasattr(p, 'xq'):                       # (hrf_attn_block_t; hrf_ffn_eval_t has neither)
+                if hasattr(p, 'xq'):                       # (hrf_attn_block_t / hrf_attn_proj_t; hrf_ffn_eval_t has neither)
                     d['cross'] = int(p.xq != p.xkv)
-                    d['w1'] = int(bool(p.w1))
+                    if hasattr(p, 'w1'):
+                        d['w1'] = int(bool(p.w1))
+                    if hasattr(p, 'q_out'):                # (hrf_attn_proj_t: a training forward stores q | k | v)
+                        d['store'] = int(bool(p.q_out or p.k_out or p.v_out))
             return d
 
         if name in _lib._RAW_RETURN or name in ('hrf_wgrad_group_begin', 'hrf_wgrad_group_end', 'hrf_debug_knob', 'hrf_group_begin',
@@ -193,7 +203,7 @@ def shape_tag(name, a):
     """Human-readable signature of one launch: entry point + the shape/mode integers that select the
     kernel variant (pointer arguments reduced to present/absent).  Also the key of profiles/*traffic*.json."""
     keep = ('B', 'H', 'W', 'C', 'Cin', 'Cout', 'KH', 'stride', 'rows', 'heads', 'tf_mode', 'epi', 'mode', 'accumulate', 'cross', 'w1',
-            'nwin')
+            'store', 'nwin')
     parts = [f'{k}={a[k]}' for k in keep if k in a and isinstance(a[k], (int, float))]
     if 'cA' in a:
         parts.append(f"bnb={int(a['cA'] is not None)}")

@@ -353,7 +353,7 @@ _GROUPABLE = frozenset((
     'hrf_conv_fwd', 'hrf_conv_bwd_data', 'hrf_conv_fwd_packed', 'hrf_conv_bwd_data_packed', 'hrf_dwconv_fwd', 'hrf_dwconv_bwd_data',
     'hrf_dwconv_bwd_data_weight', 'hrf_conv_bwd_data_weight',
     'hrf_attn_block_fwd', 'hrf_attn_block_bwd', 'hrf_affine_act_res', 'hrf_act_bwd', 'hrf_scale_add', 'hrf_ln_stats',
-    'hrf_ln_bwd', 'hrf_window_attn_fwd', 'hrf_window_attn_bwd', 'hrf_fuse_sum', 'hrf_bilinear_up_bwd'))
+    'hrf_ln_bwd', 'hrf_window_attn_fwd', 'hrf_window_attn_bwd', 'hrf_window_attn_proj_fwd', 'hrf_fuse_sum', 'hrf_bilinear_up_bwd'))
 _NO_PARK = frozenset(_lib._RAW_RETURN) | frozenset((
     'hrf_wgrad_group_begin', 'hrf_wgrad_group_end', 'hrf_group_begin', 'hrf_group_end', 'hrf_debug_knob'))
 
@@ -1624,15 +1624,17 @@ class Plain:
         self.t, self.grad = t, None
 
 
-def linear_into(ctx, src, lin, out, off):
-    """out.t[:, off:off+Cout] = Linear(src).  `out` is a Plain shared by several projections."""
+def linear_into(ctx, src, lin, out, off, launch=True):
+    """out.t[:, off:off+Cout] = Linear(src).  `out` is a Plain shared by several projections.
+    launch=False: another launch fills those columns (window_attention_proj); only the backward is taped."""
     L, s = ctx.L, ctx.stream
     x, strides, (B, H, W, Cin), tf, sc, sh, rowstat = _src_desc(src)
     w, b = lin.weight, lin.bias
     Cout = w.shape[0]
     ld = out.t.shape[-1]
-    L.hrf_conv_fwd(x, *strides, B, H, W, Cin, w, b, 1, 1, Cout, out.t, ld, off, None, None, 0,
-                   tf, sc, sh, rowstat, None, _src_fin(ctx, src), None, 0.0, s)
+    if launch:
+        L.hrf_conv_fwd(x, *strides, B, H, W, Cin, w, b, 1, 1, Cout, out.t, ld, off, None, None, 0,
+                       tf, sc, sh, rowstat, None, _src_fin(ctx, src), None, 0.0, s)
 
     def bwd():
         _conv_backward(ctx, src, w, b, 1, 1, Cout, out.grad, ld, off, None, None)
@@ -1710,14 +1712,16 @@ def ln_input(ctx, act, ln, cache=None):
     return LNIn(act, rowstat, ln)
 
 
-def window_attention(ctx, q, qoff, k, koff, v, voff, kpad, vpad, kbias, kboff, vbias, vboff, rpb, heads, dims):
+def window_attention(ctx, q, qoff, k, koff, v, voff, kpad, vpad, kbias, kboff, vbias, vboff, rpb, heads, dims, launch=True):
     """softmax(q k^T d^-1/2 + RPB) v per 7x7 window and head.  q/k/v are Plain projection buffers.
-    (kbias, kboff) / (vbias, vboff): bias parameter and element offset receiving the pad-key/value grads."""
+    (kbias, kboff) / (vbias, vboff): bias parameter and element offset receiving the pad-key/value grads.
+    launch=False: another launch fills o (window_attention_proj); only the backward is taped."""
     L, s = ctx.L, ctx.stream
     B, H, W, C = dims
     o = Act(_new((B, H, W, C), q.t.device))
-    L.hrf_window_attn_fwd(q.t, q.t.shape[-1], qoff, k.t, k.t.shape[-1], koff, v.t, v.t.shape[-1], voff,
-                          kpad, vpad, rpb, o.t, C, B, H, W, C, heads, s)
+    if launch:
+        L.hrf_window_attn_fwd(q.t, q.t.shape[-1], qoff, k.t, k.t.shape[-1], koff, v.t, v.t.shape[-1], voff,
+                              kpad, vpad, rpb, o.t, C, B, H, W, C, heads, s)
 
     def bwd():
         for p in (q, k, v):
@@ -1734,6 +1738,79 @@ def window_attention(ctx, q, qoff, k, koff, v, voff, kpad, vpad, kbias, kboff, v
                               v.grad, v.grad.shape[-1], voff, kacc.reshape(-1)[kboff:], vacc.reshape(-1)[vboff:],
                               racc, cs, B, H, W, C, heads, s)
     ctx.push(bwd)
+    return o
+
+
+# ----------------------------------------------------------------------------- per-head attention with the projections inside
+# HRF_ATTN_PROJ: comma list of widths (e.g. "72,144") whose attention sites run LayerNorm + q / k / v + the attention core as ONE
+# launch of windows x heads workgroups (csrc/attention.hip attn_proj_fwd_kernel) in place of linear_into (x1 or x3) +
+# window_attention; tape-free forwards of a listed width leave the one-launch block (attn_block_ok).  Empty = off, the default:
+# tools/attn_proj_cost.py / profiles/attn_proj_cost.txt hold the per-width measurements.
+_ATTN_PROJ = frozenset(int(w) for w in os.environ.get('HRF_ATTN_PROJ', '').split(',') if w.strip())
+
+
+def attn_proj_ok(ctx, C, heads):
+    """Does this attention site take the per-head launch with the projections inside?  A listed width the kernel is not built
+    for is an error, not a silent change of route."""
+    if C not in _ATTN_PROJ:
+        return False
+    if not ctx.L.hrf_window_attn_proj_supported(C, heads):
+        raise _lib.HRFuserHipError(f'HRF_ATTN_PROJ lists width {C} ({heads} heads): hrf_window_attn_proj_fwd is not built for it')
+    return True
+
+
+def window_attention_proj(ctx, q_in, kv_in, lins, rpb, heads):
+    """window_attention(Linear_q(q_in), Linear_k(kv_in), Linear_v(kv_in)) as one launch.  q_in / kv_in: LNIn (kv_in is q_in:
+    self-attention); lins: (packed qkv Linear,) or (q_proj, k_proj, v_proj).  With a tape the launch also stores q | k | v into
+    the buffers the chain's projections fill, and the tape gets the chain's own closures (linear_into / window_attention with
+    launch=False): the backward pass is the chain's."""
+    L, s = ctx.L, ctx.stream
+    B, H, W, C = q_in.shape
+    dims = (B, H, W, C)
+    rows, dev = B * H * W, q_in.act.t.device
+    packed = len(lins) == 1
+    if packed:
+        assert kv_in is q_in
+        (wq, wk, wv), r0 = (lins[0],) * 3, (0, C, 2 * C)
+    else:
+        (wq, wk, wv), r0 = lins, (0, 0, 0)
+    bufs = None
+    if ctx.record:
+        if packed:
+            qkv = Plain(_new((rows, 3 * C), dev))
+            linear_into(ctx, q_in, wq, qkv, 0, launch=False)
+            bq = wq.bias
+            o = window_attention(ctx, qkv, 0, qkv, C, qkv, 2 * C, bq[C:2 * C], bq[2 * C:], bq, C, bq, 2 * C, rpb, heads, dims,
+                                 launch=False)
+            bufs = ((qkv, 0), (qkv, C), (qkv, 2 * C))
+        else:
+            q, kv = Plain(_new((rows, C), dev)), Plain(_new((rows, 2 * C), dev))
+            linear_into(ctx, q_in, wq, q, 0, launch=False)
+            linear_into(ctx, kv_in, wk, kv, 0, launch=False)
+            linear_into(ctx, kv_in, wv, kv, C, launch=False)
+            o = window_attention(ctx, q, 0, kv, 0, kv, C, wk.bias, wv.bias, wk.bias, 0, wv.bias, 0, rpb, heads, dims, launch=False)
+            bufs = ((q, 0), (kv, 0), (kv, C))
+    else:
+        o = Act(_new(dims, dev))
+    P = _lib._ptr
+
+    def wrow(lin, r):
+        return lin.weight.data_ptr() + 4 * r * C, (lin.bias.data_ptr() + 4 * r) if lin.bias is not None else None
+
+    a = _lib.AttnProj()
+    a.B, a.H, a.W, a.C, a.heads = B, H, W, C, heads
+    a.xq, a.xkv = P(q_in.act.t), P(kv_in.act.t)
+    a.lnq_g, a.lnq_b, a.rowstat_q = P(q_in.ln.weight), P(q_in.ln.bias), P(q_in.rowstat)
+    if kv_in is not q_in:
+        a.lnkv_g, a.lnkv_b, a.rowstat_kv = P(kv_in.ln.weight), P(kv_in.ln.bias), P(kv_in.rowstat)
+    (a.wq, a.bq), (a.wk, a.bk), (a.wv, a.bv) = wrow(wq, r0[0]), wrow(wk, r0[1]), wrow(wv, r0[2])
+    a.rpb, a.o, a.ldo = P(rpb), P(o.t), C
+    if bufs is not None:
+        (qb, qo), (kb, ko), (vb, vo) = bufs
+        a.q_out, a.ldq, a.qoff = P(qb.t), qb.t.shape[-1], qo
+        a.k_out, a.ldk, a.koff = P(kb.t), kb.t.shape[-1], ko
+        a.v_out, a.ldv, a.voff = P(vb.t), vb.t.shape[-1], vo
+    L.hrf_window_attn_proj_fwd(a, s)
     return o
 
 
@@ -1792,6 +1869,8 @@ def attn_block_ok(ctx, C, heads):
     if not _ATTN_FUSED or not ctx.L.hrf_attn_block_supported(C, heads):
         return False
     if C == 39 * heads and not _ATTN_FUSED_D39:
+        return False
+    if C in _ATTN_PROJ and not ctx.record:      # a listed width: the per-head launch (window_attention_proj) + the per-op CrossFFN
         return False
     return (not ctx.record) or bool(ctx.L.hrf_attn_block_bwd_supported(C, heads))
 

@@ -244,6 +244,32 @@ int hrf_window_attn_bwd(const float* q, int ldq, int qoff, const float* k, int l
                         float* dv, int lddv, int dvoff, float* dkpad, float* dvpad, float* drpb, long copy_stride,
                         int B, int H, int W, int C, int heads, void* stream);
 
+/* ---- per-head window attention forward with LayerNorm and the q / k / v projections in the kernel ----------------------
+ * o = attention core of hrf_window_attn_fwd applied to q = LN_q(xq) wq^T + bq, k = LN_kv(xkv) wk^T + bk, v = LN_kv(xkv) wv^T +
+ * bv in ONE launch of windows x heads workgroups: what the per-op chain runs as hrf_conv_fwd(tf_mode = LayerNorm on load) into
+ * a projection buffer + hrf_window_attn_fwd.  xq / xkv: (B*H*W, C) NHWC rows; xkv == xq: self-attention (LN_kv / rowstat_kv
+ * unused).  rowstat_*: the [rows][2] (mean, rstd) LayerNorm statistics of the rows (hrf_ln_stats or a producer's epilogue).
+ * wq / wk / wv: [C][C] row-major Linear weights (possibly rows of one packed Linear), biases nullable.  A padded token is an
+ * exact zero AFTER LayerNorm, so its key / value is the projection bias, attended and not masked.  o: (B*H*W, ldo).
+ * q_out / k_out / v_out (each nullable; (rows, ld) with a column offset as in hrf_window_attn_fwd): the UNscaled q and the k /
+ * v rows of the real tokens, exactly what hrf_window_attn_bwd and the projections' backward read - a training forward.
+ * hrf_window_attn_proj_supported: C == head_dim * heads, head_dim in {18, 39}, C <= 160.  Never allocates or synchronises;
+ * an unsupported width, a NULL required pointer or cross-attention without rowstat_kv / LN_kv: HRF_ERR_ARG before any launch. */
+typedef struct hrf_attn_proj {
+  int B, H, W, C, heads;
+  const float* xq; const float* xkv;
+  const float* lnq_g; const float* lnq_b; const float* lnkv_g; const float* lnkv_b;
+  const float* rowstat_q; const float* rowstat_kv;
+  const float* wq; const float* bq; const float* wk; const float* bk; const float* wv; const float* bv;
+  const float* rpb;
+  float* o; int ldo;
+  float* q_out; int ldq, qoff;
+  float* k_out; int ldk, koff;
+  float* v_out; int ldv, voff;
+} hrf_attn_proj_t;
+int hrf_window_attn_proj_supported(int C, int heads);
+int hrf_window_attn_proj_fwd(const hrf_attn_proj_t* p, void* stream);
+
 /* ---- fused window-attention block (csrc/attn_block.hip): the whole token-local half of an HRFormerBlock
  * (hrformer.py:365-373: norm1 -> LocalWindowSelfAttention :184-236 / WindowMSA :96-131 -> residual -> norm2 -> CrossFFN
  * layers[0] :268) or of one modality of a fusion block (hrfuser_hrformer_based.py:305-317: norm1[k] / norm2[k] ->
@@ -529,7 +555,8 @@ int hrf_wgrad_group_end(void* stream);
  * sequence of ATen launches.  Here the hot kernels take their arguments as an array of up to 4 problems (blockIdx.z selects
  * the problem; csrc/hrf_group.h): between hrf_group_begin() and hrf_group_end(stream) the launches of the calls to
  *   hrf_conv_fwd, hrf_conv_bwd_data, hrf_dwconv_fwd, hrf_dwconv_bwd_data(_weight), hrf_attn_block_fwd / _bwd,
- *   hrf_window_attn_fwd / _bwd, hrf_affine_act_res, hrf_act_bwd, hrf_scale_add, hrf_ln_stats, hrf_ln_bwd, hrf_fuse_sum,
+ *   hrf_window_attn_fwd / _bwd, hrf_window_attn_proj_fwd, hrf_affine_act_res, hrf_act_bwd, hrf_scale_add, hrf_ln_stats, hrf_ln_bwd,
+ *   hrf_fuse_sum,
  *   hrf_bilinear_up_bwd
  * are queued (their `stream` argument is ignored) and hrf_group_end issues them on `stream`: launches of the same kernel
  * instantiation and launch geometry that sit at the same position of DIFFERENT calls become ONE launch; everything else is
