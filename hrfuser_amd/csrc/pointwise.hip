@@ -1192,6 +1192,18 @@ __global__ __launch_bounds__(256) void fold_copies_kernel(const float* scratch, 
 }
 
 // ------------------------------------------------------------------------------- optimizer
+// one element of the AdamW step with the (already scaled) gradient gr: the arithmetic both optimizer kernels share
+__device__ __forceinline__ void adamw_elem(float* p, float* m, float* v, long i, float gr, float wm, float lr, float b1,
+                                           float b2, float eps, float wd, float bc1, float bc2) {
+  float pi = p[i];
+  pi -= lr * wd * wm * pi;                                       // decoupled weight decay (torch.optim.AdamW)
+  const float mi = b1 * m[i] + (1.f - b1) * gr;
+  const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
+  m[i] = mi; v[i] = vi;
+  const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
+  p[i] = pi - (lr / bc1) * (mi / denom);
+}
+
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, const float* wd_mask,
                                                     long n, float lr, float b1, float b2, float eps, float wd,
                                                     const float* state, float gscale) {
@@ -1200,20 +1212,111 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, fl
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     const float wm = wd_mask ? wd_mask[i] : 1.f;
     if (wm < 0.f) continue;                                      // parameter without a gradient (torch skips `grad is None`)
-    const float gr = g[i] * gscale;
-    float pi = p[i];
-    pi -= lr * wd * wm * pi;                                     // decoupled weight decay (torch.optim.AdamW)
-    const float mi = b1 * m[i] + (1.f - b1) * gr;
-    const float vi = b2 * v[i] + (1.f - b2) * gr * gr;
-    m[i] = mi; v[i] = vi;
-    const float denom = sqrtf(vi) / sqrtf(bc2) + eps;
-    p[i] = pi - (lr / bc1) * (mi / denom);
+    adamw_elem(p, m, v, i, g[i] * gscale, wm, lr, b1, b2, eps, wd, bc1, bc2);
+  }
+}
+
+// the same step behind a global-norm clip: clip = the float[8] adamw_tick_clip_kernel filled for this step.  The gradient
+// is rounded twice, fl(fl(g * gscale) * coef): DDP averages, then clip_grad_norm_ multiplies.
+__global__ __launch_bounds__(256) void adamw_kernel_clipped(float* p, const float* g, float* m, float* v,
+                                                            const float* wd_mask, long n, float lr, float b1, float b2,
+                                                            float eps, float wd, const float* state, float gscale,
+                                                            const float* clip) {
+  if (clip[5] != 0.f) return;                                    // a non-finite step that is skipped: p, m, v stay
+  const float bc1 = state[0], bc2 = state[1], coef = clip[0];
+  if (lr < 0.f) lr = state[3];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const float wm = wd_mask ? wd_mask[i] : 1.f;
+    if (wm < 0.f) continue;
+    const float gs = g[i] * gscale;
+    adamw_elem(p, m, v, i, gs * coef, wm, lr, b1, b2, eps, wd, bc1, bc2);
   }
 }
 
 // device-resident step counter so the optimizer stays correct under hipGraph replay
 __global__ void adamw_tick_kernel(float* state, float b1, float b2) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const float t = state[2] + 1.f;
+    state[2] = t;
+    state[0] = 1.f - powf(b1, t);
+    state[1] = 1.f - powf(b2, t);
+  }
+}
+
+// ---- global gradient norm (clip_grad_norm_, norm_type 2) without atomics: partials[b] = sum of (double)g[i]^2 over block
+// b's share of the arena.  A float's square is exact in fp64 and every sum below runs in a fixed order (per thread: grid-
+// stride passes in order, the four elements of a 16-byte load in order; per wave: xor butterfly; per block: the waves in
+// order), so a partial is a bit-exact function of the arena in every mode.  The arena is only 4-byte aligned: hrf_ld4.
+constexpr int SSQ_UNROLL = 4;                // 16-byte loads in flight per thread and operand
+constexpr long SSQ_MAX_PARTS = 1024;         // 4 blocks of 256 per CU
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int mk = 32; mk >= 1; mk >>= 1) v += __shfl_xor(v, mk);
+  return v;
+}
+
+template <bool MASK>
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* g, const float* wd_mask, long n, double* partials) {
+  __shared__ double sW[4];
+  const long nv = n >> 2, stride = (long)gridDim.x * 256;
+  double acc = 0.0;
+  for (long v0 = (long)blockIdx.x * 256 + threadIdx.x; v0 < nv; v0 += SSQ_UNROLL * stride) {
+    hrf_f4 x[SSQ_UNROLL], w[SSQ_UNROLL];
+    bool in[SSQ_UNROLL];
+#pragma unroll
+    for (int k = 0; k < SSQ_UNROLL; ++k) {
+      in[k] = v0 + k * stride < nv;
+      const long v = in[k] ? v0 + k * stride : v0;               // (past the end: a second load of the first vector, not counted)
+      x[k] = hrf_ld4(g + 4 * v);
+      if (MASK) w[k] = hrf_ld4(wd_mask + 4 * v);
+    }
+#pragma unroll
+    for (int k = 0; k < SSQ_UNROLL; ++k)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const double d = (double)x[k][e];
+        acc += (in[k] && (!MASK || w[k][e] >= 0.f)) ? d * d : 0.0;      // a select: NaN / Inf of a skipped element never enters
+      }
+  }
+  if (blockIdx.x == 0 && (long)threadIdx.x < (n & 3)) {          // scalar tail
+    const long i = 4 * nv + threadIdx.x;
+    const double d = (double)g[i];
+    acc += (!MASK || wd_mask[i] >= 0.f) ? d * d : 0.0;
+  }
+  acc = wave_sum_f64(acc);
+  if ((threadIdx.x & 63) == 0) sW[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((sW[0] + sW[1]) + sW[2]) + sW[3];
+}
+
+// finalize of the norm + the guarded step count in ONE single-wave launch (a graph node has a ~2.7 us floor).
+// clip = float[8]: {coef, total_norm, finite, skipped steps, max_norm (host-written), skip-this-step, 0, 0}.
+__global__ __launch_bounds__(64) void adamw_tick_clip_kernel(float* state, float* clip, const double* partials, int nparts,
+                                                             float gscale, int skip_nonfinite, float b1, float b2) {
+  bool skip;
+  if (nparts > 0) {
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < nparts; i += 64) acc += partials[i];
+    acc = wave_sum_f64(acc);
+    const float tn = (float)((double)gscale * sqrt(acc));        // norm of the averaged gradient
+    const float mx = clip[4];
+    float coef = 1.f;
+    if (mx > 0.f && mx <= 3.402823466e38f) {                     // (<= 0, +inf, NaN: report the norm, do not clip)
+      const float c = mx / (tn + 1e-6f);                         // torch: clamp(max_norm / (total_norm + 1e-6), max=1): NaN stays NaN
+      coef = c > 1.f ? 1.f : c;
+    }
+    const bool finite = fabsf(tn) <= 3.402823466e38f;
+    skip = skip_nonfinite && !finite;
+    if (threadIdx.x == 0) {
+      clip[0] = coef; clip[1] = tn; clip[2] = finite ? 1.f : 0.f;
+      if (skip) clip[3] += 1.f;
+      clip[5] = skip ? 1.f : 0.f; clip[6] = 0.f; clip[7] = 0.f;
+    }
+  } else {
+    skip = clip[5] != 0.f;                                       // clip is already final for this step (a second arena)
+  }
+  if (threadIdx.x == 0 && !skip) {
     const float t = state[2] + 1.f;
     state[2] = t;
     state[0] = 1.f - powf(b1, t);
@@ -1504,6 +1607,39 @@ extern "C" int hrf_adamw(float* p, const float* g, float* m, float* v, const flo
   if (n <= 0) return HRF_OK;
   HRF_LAUNCH(adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, g, m, v, wd_mask, n, lr, beta1, beta2, eps,
              weight_decay, state, grad_scale);
+  return hrf_check_launch();
+}
+
+extern "C" long hrf_grad_sumsq_parts(long n) {
+  const long p = (n + 1023) / 1024;                              // one 16-byte load per thread and block-wide pass
+  return p < 1 ? 1 : (p > SSQ_MAX_PARTS ? SSQ_MAX_PARTS : p);
+}
+
+extern "C" int hrf_grad_sumsq(const float* g, const float* wd_mask, long n, double* partials, void* stream) {
+  if (n < 0 || partials == nullptr || (n > 0 && g == nullptr)) return HRF_ERR_ARG;
+  const dim3 grid((unsigned)hrf_grad_sumsq_parts(n));
+  if (wd_mask) {
+    HRF_LAUNCH(grad_sumsq_kernel<true>, grid, dim3(256), 0, stream, g, wd_mask, n, partials);
+  } else {
+    HRF_LAUNCH(grad_sumsq_kernel<false>, grid, dim3(256), 0, stream, g, wd_mask, n, partials);
+  }
+  return hrf_check_launch();
+}
+
+extern "C" int hrf_adamw_tick_clip(float* state, float* clip, const double* partials, int nparts, float grad_scale,
+                                   int skip_nonfinite, float beta1, float beta2, void* stream) {
+  if (nparts < 0 || (nparts > 0 && partials == nullptr)) return HRF_ERR_ARG;
+  HRF_LAUNCH(adamw_tick_clip_kernel, dim3(1), dim3(64), 0, stream, state, clip, partials, nparts, grad_scale, skip_nonfinite,
+             beta1, beta2);
+  return hrf_check_launch();
+}
+
+extern "C" int hrf_adamw_clipped(float* p, const float* g, float* m, float* v, const float* wd_mask, long n, float lr,
+                                 float beta1, float beta2, float eps, float weight_decay, const float* state,
+                                 float grad_scale, const float* clip, void* stream) {
+  if (n <= 0) return HRF_OK;
+  HRF_LAUNCH(adamw_kernel_clipped, dim3(ew_grid(n)), dim3(256), 0, stream, p, g, m, v, wd_mask, n, lr, beta1, beta2, eps,
+             weight_decay, state, grad_scale, clip);
   return hrf_check_launch();
 }
 

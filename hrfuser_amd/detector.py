@@ -75,13 +75,17 @@ class ExtractTrainer:
 
     Same contract as `Trainer` (synthetic loss L = sum_i <pyramid_i, cot_i>, flat-arena gradient all-reduce, fused
     AdamW with the reference's `paramwise_cfg` decay mask), with the neck's arena exchanged and stepped beside the
-    backbone's."""
+    backbone's.  max_norm / norm_type / skip_nonfinite as for `Trainer`, with ONE norm over both arenas (mmcv clips the whole
+    model at once): the two hrf_grad_sumsq launches fill one partials buffer, one hrf_adamw_tick_clip finalises it and both
+    hrf_adamw_clipped launches read the same `clip`."""
 
     def __init__(self, feats, group=None, world_size=1, **opt):
         assert feats.with_neck
         self.feats = feats
         self.tb = Trainer(feats.backbone, group=group, world_size=world_size, **opt)
         self.tn = Trainer(feats.neck, group=group, world_size=world_size, **opt)
+        self.clipping = self.tb.clipping
+        self.clip = None                     # the device float[8] both arenas share (Trainer.clip)
         self.group, self.world = group, world_size
         self.graph = None
         self._graph_mm = None                # the neck's matrix mode the graph was captured in
@@ -92,6 +96,9 @@ class ExtractTrainer:
         if not self.tb._ready:
             self.tb._setup(x.device)
             self.tn._setup(x.device)
+            if self.clipping:
+                self.clip = self.tn.clip = self.tb.clip
+                self._partials = torch.zeros(self.tb._nparts + self.tn._nparts, device=x.device, dtype=torch.float64)
         R.gpu_zero_(eb.flat_g)
         R.gpu_zero_(en.flat_g)
         cb, outs, _ = net._execute((x,) + tuple(mods), True)
@@ -108,21 +115,58 @@ class ExtractTrainer:
             o.grad = s_.grad
         cb.run_backward()
         L = _lib.lib()
-        for tr, eng in ((self.tb, eb), (self.tn, en)):
+        pairs = ((self.tb, eb), (self.tn, en))
+
+        def exchange(tr, eng):
             if self.world > 1 or tr.force:
                 import torch.distributed as dist
                 for a, b in tr.buckets(eng.flat_g.numel()):
                     dist.all_reduce(eng.flat_g[a:b], group=self.group)
+        if not self.clipping:
+            for tr, eng in pairs:
+                exchange(tr, eng)
+                s = _lib.stream_ptr()
+                L.hrf_adamw_tick(tr.state, tr.betas[0], tr.betas[1], s)
+                L.hrf_adamw(eng.flat_p, eng.flat_g, tr.m, tr.v, tr.wd_mask, eng.flat_p.numel(), tr.lr, tr.betas[0],
+                            tr.betas[1], tr.eps, tr.wd, tr.state, 1.0 / self.world, s)
+        else:
+            # one norm over both arenas: both exchanges first, the partial sums back to back, ONE finalize; the neck's step count
+            # advances behind it under the same skip flag (nparts = 0)
+            for tr, eng in pairs:
+                exchange(tr, eng)
             s = _lib.stream_ptr()
-            L.hrf_adamw_tick(tr.state, tr.betas[0], tr.betas[1], s)
-            L.hrf_adamw(eng.flat_p, eng.flat_g, tr.m, tr.v, tr.wd_mask, eng.flat_p.numel(), tr.lr, tr.betas[0],
-                        tr.betas[1], tr.eps, tr.wd, tr.state, 1.0 / self.world, s)
+            tb, tn = self.tb, self.tn
+            L.hrf_grad_sumsq(eb.flat_g, tb.wd_mask, eb.flat_g.numel(), self._partials, s)
+            L.hrf_grad_sumsq(en.flat_g, tn.wd_mask, en.flat_g.numel(), self._partials[tb._nparts:], s)
+            L.hrf_adamw_tick_clip(tb.state, self.clip, self._partials, tb._nparts + tn._nparts, 1.0 / self.world,
+                                  int(tb.skip_nonfinite), tb.betas[0], tb.betas[1], s)
+            L.hrf_adamw_tick_clip(tn.state, self.clip, None, 0, 1.0 / self.world, int(tn.skip_nonfinite), tn.betas[0], tn.betas[1], s)
+            for tr, eng in pairs:
+                L.hrf_adamw_clipped(eng.flat_p, eng.flat_g, tr.m, tr.v, tr.wd_mask, eng.flat_p.numel(), tr.lr, tr.betas[0],
+                                    tr.betas[1], tr.eps, tr.wd, tr.state, 1.0 / self.world, self.clip, s)
         net.params_updated()
         neck.params_updated()
         return pyr
 
     def step(self, x, mods, cots):
         return self._step_impl(x, mods, cots)
+
+    def set_max_norm(self, max_norm):
+        """Trainer.set_max_norm for the norm both arenas share (a captured graph follows it)."""
+        self.tb.set_max_norm(max_norm)
+        self.tn.max_norm = self.tb.max_norm
+
+    def grad_norm(self):
+        """Global L2 norm of the last step's averaged gradient over backbone AND neck, before clipping.  Synchronises."""
+        return self.tb.grad_norm()
+
+    def clip_coef(self):
+        """Trainer.clip_coef of the shared norm.  Synchronises."""
+        return self.tb.clip_coef()
+
+    def skipped_steps(self):
+        """Trainer.skipped_steps (both arenas skip together).  Synchronises."""
+        return self.tb.skipped_steps()
 
     def capture(self, x, mods, cots, warmup=2):
         side = torch.cuda.Stream()

@@ -143,6 +143,14 @@ def work_model(name, a):
         return 'bilinear_up_bwd_kernel', 2 * n, f4 * (n + 3.0 * a['B'] * a['Hs'] * a['Ws'] * a['C'])
     if name == 'hrf_adamw':
         return 'adamw_kernel', 12.0 * a['n'], f4 * a['n'] * 7
+    if name == 'hrf_adamw_clipped':
+        return 'adamw_kernel_clipped', 13.0 * a['n'], f4 * a['n'] * 7
+    if name == 'hrf_grad_sumsq':
+        # one pass over the arena (a second stream for the decay mask when there is one: its sign says which elements count)
+        mask = a['wd_mask'] is not None
+        return f'grad_sumsq_kernel<{"true" if mask else "false"}>', 2.0 * a['n'], f4 * a['n'] * (1 + mask)
+    if name == 'hrf_adamw_tick_clip':
+        return 'adamw_tick_clip_kernel', float(a['nparts']), 8.0 * a['nparts']
     return name.replace('hrf_', '') + '_kernel', 0.0, 0.0
 
 

@@ -1458,6 +1458,15 @@ def _conv_backward(ctx, src, weight, bias, KH, stride, Cout, dy, ldD, doff, yraw
         # weight gradients are leaves of the backward graph: issue them on a side lane so they overlap
         # the latency-bound data-gradient chain (operands are never mutated afterwards)
         bgrad = bias.grad if (bias is not None and bias.requires_grad) else None
+        if bgrad is not None and ctx.det:
+            # deterministic mode: a bias with a replicated accumulator (the attention projections: the pad-key / pad-value
+            # gradients arrive there) collects THIS leaf in the same shadow bins, so that the parameter's gradient of a pass is
+            # ONE exactly summed, once rounded addend of the arena - the two leaves of a key bias cancel analytically, and two
+            # separately rounded `+=` would leave noise at the magnitude of the partials that depends on what the arena holds
+            # (gradient accumulation, Trainer.step_accumulated)
+            bacc, bcs = ctx.owner._engine().grad_acc(bias)
+            if bcs:
+                bgrad = bacc
         xw, sw = x, strides
         if isinstance(src, RawInput) and KH == 3 and src.cols is not None:
             # the forward formed the 3x3 patches as rows (hrf_im2col3x3): grad_weight = dY^T . cols, the 1x1 form on

@@ -597,6 +597,34 @@ int hrf_adamw(float* p, const float* g, float* m, float* v, const float* wd_mask
               float beta1, float beta2, float eps, float weight_decay, const float* state,
               float grad_scale, void* stream);
 
+/* ---- global gradient-norm clipping in front of the fused AdamW (torch.nn.utils.clip_grad_norm_, norm_type 2; mmcv's
+ * OptimizerHook(grad_clip=dict(max_norm=...))) - three launches, everything on the device, no atomics in any mode:
+ *   hrf_grad_sumsq: partials[b] = sum of (double)g[i]^2 over block b's fixed share of the n floats, b < hrf_grad_sumsq_parts(n)
+ *     (a pure function of n, 1 ... 1024: the caller sizes `partials` with it).  wd_mask as in hrf_adamw: elements with
+ *     wd_mask[i] < 0 are skipped (torch skips `grad is None`), NULL = all count.  g / wd_mask need 4-byte alignment only;
+ *     any n >= 0.  fp64 sums in a fixed order (a float's square is exact in fp64): a partial is a bit-exact function of the
+ *     arena, so the deterministic mode has no second code path and every rank computes the same norm after the all-reduce.
+ *   hrf_adamw_tick_clip: one single-block launch that sums partials[0 .. nparts) in a fixed order (the partials of several
+ *     arenas may lie back to back), fills clip and advances the step count.  clip = float[8] on the device:
+ *       [0] coef  [1] total_norm  [2] finite (1 / 0)  [3] count of skipped steps  [4] max_norm  [5] skip this step  [6..7] 0
+ *     clip[4] is written by the HOST (a device value, so a captured hipGraph follows it); <= 0 or +inf = report the norm, do
+ *     not clip (coef = 1).  total_norm = float(grad_scale * sqrt(sum)) in fp64 - the norm of the AVERAGED gradient, finite
+ *     wherever the fp64 sum is (torch's fp32 norm overflows from elements of ~1e19 on); coef = min(1, max_norm /
+ *     (total_norm + 1e-6f)) in fp32 as torch computes it (a NaN norm gives a NaN coef, an Inf norm coef 0).  finite =
+ *     isfinite(total_norm).  skip_nonfinite != 0 and finite == 0: clip[5] = 1, clip[3] += 1 and `state` is NOT advanced;
+ *     otherwise clip[5] = 0 and state advances as in hrf_adamw_tick.  nparts == 0: clip is already final for this step -
+ *     clip[0..5] stay, state advances unless clip[5] is set (the tick of a second arena that shares the norm).
+ *   hrf_adamw_clipped: hrf_adamw with the gradient fl(fl(g[i] * grad_scale) * clip[0]) - two fp32 roundings in that order:
+ *     DDP averages, then clip_grad_norm_ multiplies (coef == 1: bit-equal to hrf_adamw); returns without touching p, m, v
+ *     when clip[5] != 0.                                                                                              */
+long hrf_grad_sumsq_parts(long n);
+int hrf_grad_sumsq(const float* g, const float* wd_mask, long n, double* partials, void* stream);
+int hrf_adamw_tick_clip(float* state, float* clip, const double* partials, int nparts, float grad_scale,
+                        int skip_nonfinite, float beta1, float beta2, void* stream);
+int hrf_adamw_clipped(float* p, const float* g, float* m, float* v, const float* wd_mask, long n, float lr,
+                      float beta1, float beta2, float eps, float weight_decay, const float* state,
+                      float grad_scale, const float* clip, void* stream);
+
 /* The digest (sha256, 64 hex characters) of the sources, headers, flags and target this library was built from
  * (hrfuser_amd/build_ext.py compares it with the tree on every build(): a source change is never paired with an old binary). */
 const char* hrf_build_digest(void);
