@@ -59,6 +59,7 @@ BnBFin = struct_from_header('hrf_bn_bfin')          # BatchNorm-backward coeffic
 AttnBlock = struct_from_header('hrf_attn_block')    # fused window-attention block (csrc/attn_block.hip)
 AttnProj = struct_from_header('hrf_attn_proj')      # per-head attention forward with LayerNorm + q / k / v in the kernel (csrc/attention.hip)
 FfnEval = struct_from_header('hrf_ffn_eval')        # eval-mode CrossFFN in one launch (csrc/ffn_eval.hip)
+BottleneckEval = struct_from_header('hrf_bottleneck_eval')   # eval-mode Bottleneck in one launch (csrc/hrf_bneck_eval.h)
 Conv3xPackJob = struct_from_header('hrf_conv3x_pack_job')   # one weight tensor of hrf_conv3x_pack (csrc/conv3x_engine.hip)
 P2p = struct_from_header('hrf_p2p')                 # peer-to-peer SyncBN exchange context (csrc/p2p_exchange.hip)
 
@@ -68,7 +69,7 @@ def _ptr(t):
 
 
 _RAW_RETURN = ('hrf_conv3_wgrad_wide_scratch', 'hrf_conv_bwd_weight_scratch', 'hrf_conv3x_pack_size', 'hrf_conv3x_supported', 'hrf_conv_bwd_data_weight_supported', 'hrf_conv_fwd_split_scratch', 'hrf_wgrad_group_report', 'hrf_attn_block_supported', 'hrf_attn_block_bwd_supported', 'hrf_window_attn_proj_supported', 'hrf_group_count',
-               'hrf_ffn_eval_supported', 'hrf_get_deterministic', 'hrf_det_bins_bytes', 'hrf_conv3_bf16x3_supported', 'hrf_grad_sumsq_parts')       # return a value, not a status
+               'hrf_ffn_eval_supported', 'hrf_bottleneck_eval_supported', 'hrf_get_deterministic', 'hrf_det_bins_bytes', 'hrf_conv3_bf16x3_supported', 'hrf_grad_sumsq_parts')       # return a value, not a status
 _ERR = {1: 'HRF_ERR_ARG (bad argument)', 2: 'HRF_ERR_LAUNCH (kernel launch failed)'}
 
 

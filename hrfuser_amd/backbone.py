@@ -615,6 +615,14 @@ class EngineOwner:
         if hasattr(self, 'reset_graphs'):
             self.reset_graphs()
 
+    def set_bottleneck_eval(self, on=True):
+        """Eval-mode Bottleneck route of THIS net (opt-in; HRF_BNECK_EVAL=1 is the initial state): a tape-free eval forward
+        runs each 64-plane Bottleneck of layer1 as one launch (runtime.bottleneck_eval, csrc/hrf_bneck_eval.h) instead of
+        four / five.  Captured module graphs are dropped - a graph replays the route it was captured on."""
+        self.__dict__['_hrf_bneck_eval'] = bool(on)
+        if hasattr(self, 'reset_graphs'):
+            self.reset_graphs()
+
     def params_updated(self):
         """Kept for callers that signal a weight update; nothing is cached across steps any more."""
 
@@ -636,6 +644,9 @@ class Bottleneck(nn.Module):
         self.downsample = downsample
 
     def run(self, ctx, x):
+        if R.bottleneck_eval_ok(ctx, self, x):
+            # tape-free eval forward, route switched on (net.set_bottleneck_eval): the whole block in one launch, y1 / y2 in LDS
+            return R.bottleneck_eval(ctx, x, self)
         n1, n2, n3 = (getattr(self, k) for k in self._nn)
         y = R.conv_bn(ctx, x, self.conv1, n1, R.TF_RELU)
         y = R.conv_bn(ctx, y, self.conv2, n2, R.TF_RELU)

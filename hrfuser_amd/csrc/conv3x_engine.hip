@@ -540,3 +540,6 @@ extern "C" int hrf_conv3x_pack(const hrf_conv3x_pack_job_t* jobs, int n, void* s
   }
   return hrf_check_launch();
 }
+
+// eval-mode Bottleneck in one launch (hrf_bottleneck_eval): the same block geometry, LDS layouts and hrf_mfma32 as above
+#include "hrf_bneck_eval.h"

@@ -111,6 +111,12 @@ def work_model(name, a):
         slot = 4 * C * C + (4 * C * C if ffn else 0)
         by = f4 * (rows * C * (4 + 3 * cross + (8 if ffn else 0)) + nwin * (slot + heads * 49 * 49)) + wts
         return f'attn_block_bwd_kernel<{C}, {heads}>', 3.0 * fwd, by
+    if name == 'hrf_bottleneck_eval':
+        # eval-mode Bottleneck in one launch: the three (four) convolutions at M = B H W without the halo recompute of conv1;
+        # x in, out and the weights (the 64-channel intermediates stay on the chip)
+        M, Cin, pl, ds = float(a['B']) * a['H'] * a['W'], a['Cin'], a['planes'], bool(a['has_downsample'])
+        wts = Cin * pl + 9 * pl * pl + 4 * pl * pl + (4 * pl * Cin if ds else 0)
+        return f'bneck_eval_kernel<{"true" if ds else "false"}>', 2.0 * M * wts, f4 * (M * Cin + M * 4 * pl + wts)
     if name == 'hrf_rpb_grad':
         return 'rpb_grad_kernel', 0.0, f4 * a['nwin'] * a['heads'] * 49 * 49
     if name == 'hrf_conv3_packed_bf16x3':
@@ -175,7 +181,7 @@ class ProfLib:
             if isinstance(p, ctypes.Structure):           # struct-argument entry points: the shape lives in the struct
                 for f, _ in p._fields_:
                     v = getattr(p, f)
-                    if f in ('B', 'H', 'W', 'C', 'heads', 'hidden'):
+                    if f in ('B', 'H', 'W', 'C', 'heads', 'hidden', 'Cin', 'planes', 'has_downsample'):
                         d[f] = v
                 if hasattr(p, 'xq'):                       # (hrf_attn_block_t / hrf_attn_proj_t; hrf_ffn_eval_t has neither)
                     d['cross'] = int(p.xq != p.xkv)

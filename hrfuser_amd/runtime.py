@@ -1864,6 +1864,63 @@ def ffn_eval(ctx, x, ln, ffn):
     return out
 
 
+# ----------------------------------------------------------------------------- eval-mode Bottleneck in one launch
+# OPT-IN (HRF_BNECK_EVAL=1 is the initial state of every net, net.set_bottleneck_eval(on) switches one net): the measured
+# outcome is in README.md / DESIGN.md section 15 (tools/bneck_eval_cost.py, profiles/bneck_eval_cost.txt)
+_BNECK_EVAL = os.environ.get('HRF_BNECK_EVAL', '0') == '1'
+
+
+def bottleneck_eval_ok(ctx, blk, x=None):
+    """Can this Bottleneck run as ONE launch (csrc/hrf_bneck_eval.h)?  Only when the route is switched on, without a tape
+    (an eval forward: nothing will back-propagate through it), with every BatchNorm of the block frozen (eval mode: running
+    statistics as a per-channel affine; GroupNorm and `norm_eval=True` TRAINING keep the per-op chain), on a materialised
+    dense NHWC input and for the shapes the kernel is built for (the two blocks of layer1: 64 planes)."""
+    on = ctx.owner.__dict__.get('_hrf_bneck_eval')
+    if not (_BNECK_EVAL if on is None else on) or ctx.record or ctx.training or ctx.probe is not None:
+        return False
+    ds = blk.downsample
+    norms = [getattr(blk, k) for k in blk._nn] + ([ds[1]] if ds is not None else [])
+    if any(is_gn(n) or n.training or getattr(n, 'running_mean', None) is None for n in norms):
+        return False
+    convs = [blk.conv1, blk.conv2, blk.conv3] + ([ds[0]] if ds is not None else [])
+    if any(c.bias is not None or c.groups != 1 or c.stride != (1, 1) for c in convs):
+        return False
+    planes, Cin = blk.conv1.weight.shape[:2]
+    if tuple(blk.conv3.weight.shape[:2]) != (4 * planes, planes) or (ds is not None and tuple(ds[0].weight.shape) != (4 * planes, Cin, 1, 1)):
+        return False
+    if x is not None and not (isinstance(x, Act) and x.t.dim() == 4 and x.t.shape[3] == Cin and x.t.is_contiguous()):
+        return False
+    eng = ctx.owner._engine()
+    if not hasattr(eng, 'packed') or eng.packed(blk.conv2.weight, 0) is None:
+        return False
+    return ctx.L.hrf_bottleneck_eval_supported(int(Cin), int(planes), 1 if ds is not None else 0) == 1
+
+
+def bottleneck_eval(ctx, x, blk):
+    """ReLU(BN3(conv3(ReLU(BN2(conv2(ReLU(BN1(conv1(x)))))))) + identity)  (resnet.py:263-302 with frozen BatchNorms): one
+    launch, the two 64-channel intermediates stay on the chip.  The affines are applied in the kernel's epilogues and conv2
+    reads the tap-major pack the engine refreshes every forward - nothing derived from the weights is cached."""
+    B, H, W, Cin = x.t.shape
+    eng = ctx.owner._engine()
+    P = _lib._ptr
+    ds = blk.downsample
+    planes = blk.conv1.weight.shape[0]
+    a = _lib.BottleneckEval()
+    a.B, a.H, a.W, a.Cin, a.planes, a.has_downsample = B, H, W, Cin, planes, 1 if ds is not None else 0
+    a.x = P(x.t)
+    (s1, t1, _, _), (s2, t2, _, _), (s3, t3, _, _) = (eng.bn_eval_affine(getattr(blk, k)) for k in blk._nn)
+    a.w1, a.s1, a.t1 = P(blk.conv1.weight), P(s1), P(t1)
+    a.w2, a.s2, a.t2 = P(eng.packed(blk.conv2.weight, 0)), P(s2), P(t2)
+    a.w3, a.s3, a.t3 = P(blk.conv3.weight), P(s3), P(t3)
+    if ds is not None:
+        sd, td, _, _ = eng.bn_eval_affine(ds[1])
+        a.wd, a.sd, a.td = P(ds[0].weight), P(sd), P(td)
+    out = Act(_new((B, H, W, 4 * planes), x.t.device))
+    a.out = P(out.t)
+    ctx.L.hrf_bottleneck_eval(a, ctx.stream)
+    return out
+
+
 # ----------------------------------------------------------------------------- fused window-attention block
 _ATTN_FUSED = os.environ.get('HRF_ATTN_FUSED', '1') != '0'
 # head_dim 39 widths (HRFuser-B / HRFormer-B 78 / 156; forward-only kernels, so tape-free forwards only): OFF by default.  Measured on

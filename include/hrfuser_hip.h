@@ -351,6 +351,31 @@ typedef struct hrf_ffn_eval {
 } hrf_ffn_eval_t;
 int hrf_ffn_eval_supported(int C, int hidden);
 int hrf_ffn_eval(const hrf_ffn_eval_t* p, void* stream);
+
+/* ---- eval-mode Bottleneck in one launch (csrc/hrf_bneck_eval.h, part of csrc/conv3x_engine.hip) --------------------------
+ * resnet.py:263-302 with every BatchNorm FROZEN (eval mode / norm_eval: running statistics as a per-channel affine):
+ *   y1  = ReLU(s1 * conv1x1(x;  w1 [planes][Cin])        + t1)
+ *   y2  = ReLU(s2 * conv3x3(y1; w2, pad 1, stride 1)     + t2)
+ *   idt = has_downsample ? sd * conv1x1(x; wd [4 planes][Cin]) + td : x
+ *   out = ReLU(s3 * conv1x1(y2; w3 [4 planes][planes])   + t3 + idt)
+ * x: (B,H,W,Cin), out: (B,H,W,4 planes), dense NHWC fp32.  No convolution has a bias; w1, w3, wd in their Conv2d layouts, w2 =
+ * the direction-0 tap-major pack of hrf_conv3x_pack (wp[tap][n][k]); (s_k, t_k) = the frozen-statistics affine of BatchNorm k
+ * (scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale), applied in the epilogues - nothing derived
+ * from the weights is cached.  y1 at a halo position outside the image is zero (the padding of conv2).  Neither 64-channel
+ * intermediate leaves the chip.  hrf_bottleneck_eval_supported: planes == 64 and (Cin == 256 without, Cin == 64 with the
+ * downsample) - the two blocks of layer1 of every reference config; anything else, a null required pointer (wd / sd / td are
+ * required with the downsample only) or B / H / W < 1: HRF_ERR_ARG before anything is launched.                          */
+typedef struct hrf_bottleneck_eval {
+  int B, H, W, Cin, planes, has_downsample;
+  const float* x;
+  const float* w1; const float* s1; const float* t1;
+  const float* w2; const float* s2; const float* t2;
+  const float* w3; const float* s3; const float* t3;
+  const float* wd; const float* sd; const float* td;
+  float* out;
+} hrf_bottleneck_eval_t;
+int hrf_bottleneck_eval_supported(int Cin, int planes, int has_downsample);
+int hrf_bottleneck_eval(const hrf_bottleneck_eval_t* p, void* stream);
 /* the same gather for EVERY fused layer of a step in one launch: seg = nseg rows of 5 longs on the device {offset (floats) of the
  * layer's ds_plane in `planes`, windows, heads, address of its drpb accumulator, copy_stride}; max_nwin / max_heads = the
  * largest of the rows (launch geometry).                                                                               */
