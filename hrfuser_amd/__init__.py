@@ -12,5 +12,8 @@ from .backbone import (HRFuserHRFormerBased, HRFuserHRNetBased, HRFormer, HRFuse
 from .registry import NECKS                                # noqa: F401,E402
 from .neck import HRFPN, build_neck                        # noqa: F401,E402
 from .pipeline import DeviceInputPipeline                  # noqa: F401,E402
+from .registry import ROI_EXTRACTORS                       # noqa: F401,E402
+from .roi import SingleRoIExtractor, roi_align, build_roi_extractor   # noqa: F401,E402
 
-__all__ = ['BACKBONES', 'NECKS', 'build_backbone', 'build_neck', 'HRFuserHRFormerBased', 'HRFuserHRNetBased', 'HRFormer', 'HRFPN']
+__all__ = ['BACKBONES', 'NECKS', 'build_backbone', 'build_neck', 'HRFuserHRFormerBased', 'HRFuserHRNetBased', 'HRFormer', 'HRFPN',
+           'ROI_EXTRACTORS', 'SingleRoIExtractor', 'roi_align', 'build_roi_extractor']

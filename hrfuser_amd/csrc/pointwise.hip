@@ -1729,3 +1729,6 @@ extern "C" int hrf_memset(void* ptr, int value, long bytes, void* stream) {
   return hipMemsetAsync(ptr, value, (size_t)bytes, (hipStream_t)stream) == hipSuccess ? HRF_OK : HRF_ERR_LAUNCH;
 #endif
 }
+
+// multi-level RoIAlign (SingleRoIExtractor) forward / backward: hrf_roi_align_fwd / _bwd
+#include "hrf_roi.h"

@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import runtime as R
-from .registry import BACKBONES, NECKS
+from .registry import BACKBONES, NECKS, ROI_EXTRACTORS
 from .trainer import Trainer
 
 
@@ -24,13 +24,17 @@ def combine_mod_imgs(lidar_img=None, radar_img=None, gated_img=None):
 
 
 class FeatureExtractor(nn.Module):
-    """backbone (+ neck) of a `TwoStageDetector` config: `FeatureExtractor(cfg.model.backbone, cfg.model.neck)`."""
+    """backbone (+ neck) of a `TwoStageDetector` config: `FeatureExtractor(cfg.model.backbone, cfg.model.neck)`;
+    `bbox_roi_extractor` (optional): the `roi_head.bbox_roi_extractor` dict of the config (hrfuser_amd.roi)."""
 
-    def __init__(self, backbone, neck=None):
+    def __init__(self, backbone, neck=None, bbox_roi_extractor=None):
         super().__init__()
         self.backbone = BACKBONES.build(backbone) if isinstance(backbone, dict) else backbone      # two_stage.py:41
         if neck is not None:
             self.neck = NECKS.build(neck) if isinstance(neck, dict) else neck                       # two_stage.py:43-44
+        if bbox_roi_extractor is not None:                                                          # standard_roi_head.py:25
+            self.bbox_roi_extractor = (ROI_EXTRACTORS.build(bbox_roi_extractor) if isinstance(bbox_roi_extractor, dict)
+                                       else bbox_roi_extractor)
 
     @property
     def with_neck(self):
@@ -56,6 +60,14 @@ class FeatureExtractor(nn.Module):
         if self.with_neck:
             x = self.neck(x)
         return x
+
+    def extract_roi_feats(self, img, rois, lidar_img=None, radar_img=None, gated_img=None):
+        """extract_feat followed by the RoI extractor (standard_roi_head.py:116-118: `bbox_roi_extractor(x[:num_inputs],
+        rois)`): rois (K,5) = (batch index, x1, y1, x2, y2) -> (K, out_channels, 7, 7)."""
+        if getattr(self, 'bbox_roi_extractor', None) is None:
+            raise ValueError('FeatureExtractor.extract_roi_feats: built without a bbox_roi_extractor')
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        return self.bbox_roi_extractor(x, rois)
 
     def forward(self, img, lidar_img=None, radar_img=None, gated_img=None):
         """The feature part of forward_train (two_stage.py:156-160): sensors by keyword."""

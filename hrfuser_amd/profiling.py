@@ -119,6 +119,15 @@ def work_model(name, a):
         return f'bneck_eval_kernel<{"true" if ds else "false"}>', 2.0 * M * wts, f4 * (M * Cin + M * 4 * pl + wts)
     if name == 'hrf_rpb_grad':
         return 'rpb_grad_kernel', 0.0, f4 * a['nwin'] * a['heads'] * 49 * 49
+    if name in ('hrf_roi_align_fwd', 'hrf_roi_align_bwd'):
+        # multi-level RoIAlign, priced by traffic: the boxes live on the device, so the footprint is an ESTIMATE - a box mapped to
+        # its level spans 14 .. 28 pixels per side there (scale in [56, 112) * 2^l at stride 4 * 2^l): (21 + 2)^2 pixels of C
+        # floats, capped by the largest map; tools/roi_align_cost.py computes the true footprints of its boxes.  Forward: the
+        # footprints read + K * 49 * C written; backward: dout read + the footprint bytes added with fp32 atomics.
+        K, C = float(a['K']), a['C']
+        fp = K * min(23.0 * 23.0, float(a.get('HW0', 23 * 23))) * C
+        fl = 2.0 * K * 49 * C * 4 * 4                     # ~2 x 2 samples of 4 corners per bin
+        return ('roi_align_fwd_kernel' if name.endswith('fwd') else 'roi_align_bwd_kernel'), fl, f4 * (fp + K * 49 * C)
     if name == 'hrf_conv3_packed_bf16x3':
         # bf16x3 matrix mode of the wide 3x3 engine: the algorithmic work of the convolution (one multiply-add per term, whatever
         # the three split products cost - MFMA_ROOF prices those) and its fp32 rows and pack
@@ -189,6 +198,9 @@ class ProfLib:
                         d['w1'] = int(bool(p.w1))
                     if hasattr(p, 'q_out'):                # (hrf_attn_proj_t: a training forward stores q | k | v)
                         d['store'] = int(bool(p.q_out or p.k_out or p.v_out))
+            lv = d.get('lv')
+            if isinstance(lv, ctypes.Structure):          # hrf_roi_levels_t: channels, batch and the finest map
+                d['C'], d['B'], d['H'], d['W'], d['HW0'] = lv.C, lv.B, lv.H[0], lv.W[0], lv.H[0] * lv.W[0]
             return d
 
         if name in _lib._RAW_RETURN or name in ('hrf_wgrad_group_begin', 'hrf_wgrad_group_end', 'hrf_debug_knob', 'hrf_group_begin',

@@ -63,6 +63,7 @@ def _resolve():
 BACKBONES, USING_MMDET = _resolve()
 MODELS = BACKBONES
 NECKS = MODELS            # mmdet 2.19: BACKBONES = NECKS = ... = MODELS (mmdet/models/builder.py:7-15)
+ROI_EXTRACTORS = MODELS   # (the same alias: builder.py:11)
 
 
 def build_backbone(cfg):

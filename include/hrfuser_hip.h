@@ -376,6 +376,54 @@ typedef struct hrf_bottleneck_eval {
 } hrf_bottleneck_eval_t;
 int hrf_bottleneck_eval_supported(int Cin, int planes, int has_downsample);
 int hrf_bottleneck_eval(const hrf_bottleneck_eval_t* p, void* stream);
+
+/* ---- multi-level RoIAlign: SingleRoIExtractor forward / backward (csrc/hrf_roi.h, part of csrc/pointwise.hip) --------------
+ * What every reference config does with the pyramid (configs/_base_/models/cascade_rcnn_hrfuser_fpn_*_fusion.py:152-156,
+ * once per cascade stage): SingleRoIExtractor.forward (mmdet/models/roi_heads/roi_extractors/single_level_roi_extractor.py:
+ * 57-108) = map_roi_levels (:36-55) + mmcv.ops.RoIAlign(output_size 7, sampling_ratio 0, pool_mode 'avg', aligned True) per
+ * level, and their autograd backward.  ONE launch serves all levels: the kernel derives each box's level itself -
+ *   scale = sqrt((x2 - x1) * (y2 - y1)),  lvl = clamp(floor(log2(scale / finest_scale + 1e-6)), 0, num_levels - 1)
+ * in fp32 (the log2 as comparisons against 2, 4, 8), num_levels == 1: level 0 for every box (:76-79) - so there is no host read
+ * of `rois`, no sort, no nonzero, no allocation, no synchronisation: the calls can be captured in a hipGraph.
+ *   feat[l]   the maps of one pyramid, NHWC fp32 [B][H_l][W_l] rows of pitch ld_l >= C floats (the HRFPN outputs in place);
+ *   rois      [K][5] fp32 on the device: (batch index, x1, y1, x2, y2) in image pixels, unscaled;
+ *   out       out_layout 0: [K][C][7][7] (the reference's order), 1: [K][7][7][C]; every row is written;
+ *   dfeat[l]  backward only, same shape and pitch as feat[l]: "+=" with fp32 atomics - the caller zeroes it, or it already
+ *             holds another consumer's gradient; a level no box maps to is not touched.  The box coordinates get no gradient
+ *             (as in mmcv).  The reference's `feats[i].sum() * 0.` term (DDP graph completeness) has no counterpart.
+ * Per level: x1' = x1 * spatial_scale - 0.5 (likewise y1', x2', y2'), rw = x2' - x1' (no clamp to 1), bin = rw / 7,
+ * grid = ceil(rw / 7), sample (ix) of bin pw at x1' + pw * bin + (ix + 0.5) * bin / grid; a sample outside [-1, W] (or
+ * [-1, H]) contributes 0, otherwise it is clamped to >= 0 and read bilinearly with the last row / column repeated; a bin is
+ * the sum of its samples / max(grid_h * grid_w, 1); a box with grid_h <= 0 or grid_w <= 0 produces zeros.  The sample
+ * positions are evaluated in fp64 (mmcv: fp32), the sums in fp32.
+ * DELIBERATE DEVIATION (the coordinates are unvalidated device data; trip counts are bounded by the map, never by the box): a
+ * box with a coordinate that is not finite, with |coordinate * spatial_scale| > HRF_ROI_COORD_MAX, or with a batch index outside
+ * [0, B) gives a row of zeros forward and contributes nothing backward (the reference reads out of bounds or returns garbage).
+ * For every other box the sample loops are clipped to the samples that can fall inside the map: at most
+ * 2 n + HRF_ROI_AXIS_SLACK sample iterations per axis of n pixels and box, whatever the box is.
+ * hrf_roi_align_supported(C, pooled, num_levels): C % 4 == 0, 4 <= C <= HRF_ROI_MAX_C, pooled == 7, 1 <= num_levels <=
+ * HRF_ROI_MAX_LEVELS.  Anything else - also `pooled` of the struct != 7, B / H_l / W_l < 1, ld_l < C, a null map, an out_layout
+ * other than 0 / 1, maps whose weight tables do not fit the LDS (H_l + W_l beyond ~3 700 at C = 256) - is HRF_ERR_ARG before
+ * any launch.  K == 0: HRF_OK, no launch.
+ * hrf_roi_align_fwd has no atomics: bit-reproducible in any mode.  hrf_roi_align_bwd is REFUSED in deterministic mode (below).   */
+#define HRF_ROI_MAX_LEVELS 4
+#define HRF_ROI_MAX_C 256
+#define HRF_ROI_COORD_MAX 1048576.0f
+#define HRF_ROI_AXIS_SLACK 40
+typedef struct hrf_roi_levels {
+  int num_levels, C, B;
+  const float* feat[HRF_ROI_MAX_LEVELS];
+  float* dfeat[HRF_ROI_MAX_LEVELS];
+  int H[HRF_ROI_MAX_LEVELS];
+  int W[HRF_ROI_MAX_LEVELS];
+  int ld[HRF_ROI_MAX_LEVELS];
+  float spatial_scale[HRF_ROI_MAX_LEVELS];
+  float finest_scale;
+  int pooled;                    /* output_size: 7 */
+} hrf_roi_levels_t;
+int hrf_roi_align_supported(int C, int pooled, int num_levels);
+int hrf_roi_align_fwd(const hrf_roi_levels_t* lv, const float* rois, int K, float* out, int out_layout, void* stream);
+int hrf_roi_align_bwd(const hrf_roi_levels_t* lv, const float* rois, int K, const float* dout, int out_layout, void* stream);
 /* the same gather for EVERY fused layer of a step in one launch: seg = nseg rows of 5 longs on the device {offset (floats) of the
  * layer's ds_plane in `planes`, windows, heads, address of its drpb accumulator, copy_stride}; max_nwin / max_heads = the
  * largest of the rows (launch geometry).                                                                               */
@@ -687,7 +735,9 @@ const char* hrf_build_digest(void);
  *       hrf_conv3_wgrad_wide with a bias gradient (the HRFPN neck's output convolutions);
  *       hrf_gn_moments (GroupNorm);
  *       hrf_p2p_exchange (SyncBN over more than one rank: the cross-rank order is out of scope; the one-rank path through
- *       hrf_bn_pack / hrf_bn_finalize_packed works). */
+ *       hrf_bn_pack / hrf_bn_finalize_packed works);
+ *       hrf_roi_align_bwd (fp32 atomics into whole activation maps: shadow bins of 32 bytes per element are out of proportion,
+ *       an order-independent backward is not built; hrf_roi_align_fwd has no atomics and is the same bits in either mode). */
 int hrf_set_deterministic(int on);
 int hrf_get_deterministic(void);
 long hrf_det_bins_bytes(long n);

@@ -37,6 +37,14 @@ int hrf_stamp(long long* dst, void* stream);
  * hrfuser_amd/backbone.py; tools/race_check.py perturbs lane timing with it). */
 int hrf_debug_spin(long ticks, void* stream);
 
+#ifdef HRF_EMUL
+/* CPU-emulator build only (tests): loop iterations of the RoIAlign kernels (csrc/hrf_roi.h) since the last reset, both launches:
+ * out2[0] = sample-loop iterations of the weight-table builds (per box and axis of n pixels at most 2 n + HRF_ROI_AXIS_SLACK,
+ * whatever the box is), out2[1] = footprint pixels visited.  reset != 0: back to zero.  (void: not a status - the ctypes binding
+ * derives its prototypes from the `int` / `long` declarations of this header and must not look for this symbol in the product.) */
+void hrf_roi_debug_iters(long* out2, int reset);
+#endif
+
 #ifdef __cplusplus
 }
 #endif
