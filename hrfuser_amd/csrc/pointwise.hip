@@ -4,6 +4,7 @@
 //   ln_stats / ln_bwd               LayerNorm row statistics and backward (channel-last rows)
 //   affine_act_res / act_bwd        BN-apply + activation + residual materialisation and its adjoint
 //   fuse_sum / bilinear_up_bwd      HRModule cross-resolution exchange (hrnet.py:184-207)
+//   fuse_sum_bwd                    the whole backward of one exchange sum in one launch
 //   adamw                           fused flat-buffer AdamW step
 //
 // Reference ops replaced: F.batch_norm, F.layer_norm, F.relu/gelu, torch.add, F.interpolate
@@ -890,6 +891,87 @@ __global__ __launch_bounds__(256) void fuse_sum_kernel(HrfGroup<FuseArgs> grp) {
   }
 }
 
+// The same sum with VW consecutive channels per thread (C % VW == 0): the pixel coordinates (three integer divisions) and the
+// bilinear sources and weights (bil_src: a float division each) once per (pixel, term) instead of once per element and term, 1 / VW
+// of the memory instructions.  Every output element keeps the arithmetic and the association of fuse_sum_kernel: bit-equal output.
+template <int VW>
+__global__ __launch_bounds__(256) void fuse_sum_vec_kernel(HrfGroup<FuseArgs> grp) {
+  const FuseArgs& a = grp.sel();
+  __shared__ float sFin[4 * HRF_FIN_MAXC];
+  bool any = false;
+  const float* tsc[4];
+  const float* tsh[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    tsc[k] = a.t[k].sc; tsh[k] = a.t[k].sh;
+    if (a.fin[k].stats != nullptr) {
+      float* base = sFin + k * HRF_FIN_MAXC;
+      hrf_bn_fin_onload(a.fin[k], base, base + HRF_FIN_MAXC / 2, threadIdx.x, 256, blockIdx.x == 0);
+      tsc[k] = base; tsh[k] = base + HRF_FIN_MAXC / 2;
+      any = true;
+    }
+  }
+  if (any) __syncthreads();
+  const int cg = a.C / VW;
+  const long items = (long)a.B * a.H * a.W * cg;
+  auto body = [&](auto i) {
+    const auto pix = i / cg;
+    const int c = (int)(i - pix * cg) * VW;
+    const auto prow = pix / a.W;
+    const int x = (int)(pix - prow * a.W), b = (int)(prow / a.H), y = (int)(prow - (decltype(prow))b * a.H);
+    const long e0 = (long)pix * a.C + c;
+    float acc[VW];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) acc[e] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const FuseTerm& t = a.t[k];
+      if (t.type == 1) {
+        float v[VW];
+        hrf_ldv<VW>(t.p + e0, v);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) acc[e] += v[e];
+      } else if (t.type == 2) {
+        float v[VW];
+        hrf_ldv<VW>(t.p + e0, v);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) acc[e] += fmaf(v[e], tsc[k][c + e], tsh[k][c + e]);
+      } else if (t.type == 3) {
+        int y0, y1, x0, x1; float wy, wx;
+        bil_src(y, t.Hs, a.H, y0, y1, wy);
+        bil_src(x, t.Ws, a.W, x0, x1, wx);
+        const float* base = t.p + (long)b * t.Hs * t.Ws * a.C + c;
+        float v00[VW], v01[VW], v10[VW], v11[VW];
+        hrf_ldv<VW>(base + ((long)y0 * t.Ws + x0) * a.C, v00);
+        hrf_ldv<VW>(base + ((long)y0 * t.Ws + x1) * a.C, v01);
+        hrf_ldv<VW>(base + ((long)y1 * t.Ws + x0) * a.C, v10);
+        hrf_ldv<VW>(base + ((long)y1 * t.Ws + x1) * a.C, v11);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) {
+          // same association as ATen upsample_bilinear2d: h0*(w0*v00 + w1*v01) + h1*(w0*v10 + w1*v11)
+          const float top = (1.f - wx) * v00[e] + wx * v01[e], bot = (1.f - wx) * v10[e] + wx * v11[e];
+          const float v = (1.f - wy) * top + wy * bot;
+          acc[e] += fmaf(v, tsc[k][c + e], tsh[k][c + e]);
+        }
+      } else if (t.type == 4) {
+        const int ys = y / (a.H / t.Hs), xs = x / (a.W / t.Ws);
+        float v[VW];
+        hrf_ldv<VW>(t.p + (((long)b * t.Hs + ys) * t.Ws + xs) * a.C + c, v);
+#pragma unroll
+        for (int e = 0; e < VW; ++e) acc[e] += fmaf(v[e], tsc[k][c + e], tsh[k][c + e]);
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < VW; ++e) acc[e] = fmaxf(acc[e], 0.f);
+    hrf_stv<VW>(a.out + e0, acc);
+  };
+  if (items * VW <= 0x7fffffffL) {
+    for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < (unsigned)items; i += gridDim.x * 256u) body(i);
+  } else {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long)gridDim.x * 256) body(i);
+  }
+}
+
 // adjoint of the nearest up-sampling by an integer factor k: du[low pixel] = sum of its k x k block of g, plus the
 // (sum du, sum du*ylow) moments of the BatchNorm in front of it; one thread = one (low-res pixel, channel) at a time
 __global__ __launch_bounds__(256) void nearest_up_bwd_kernel(const float* g, int ldG, int goff, int B, int H, int W, int C,
@@ -1065,6 +1147,230 @@ __global__ __launch_bounds__(256) void bilinear_up_bwd_kernel(HrfGroup<BilUpBwdA
     hrf_stat_add(stats, 2 * C, i, (double)t);
   }
 }
+
+// ------------------------------------------------------------------------------- backward of one exchange sum, one launch
+// hrf_fuse_sum_bwd: the grid is cut into block-uniform sections by blockIdx range - one range per up-sampled term (largest factor
+// first: its blocks live longest), each the gather of the bilinear adjoint reading dout / out directly (mask on load, so no
+// section waits for g), then the elementwise pass of act_bwd_vec_kernel (mode 0) that also writes / accumulates the identity
+// gradient.  Tensors are addressed by 32-bit BYTE offsets from the uniform base pointers (the entry point refuses rows of
+// 2^30 elements or more): half the address registers of 64-bit pointers per load in flight.
+struct FuseBwdUp { const float* ylow; float* du; double* stats; int Hs, Ws, F, L, blk0, nblk; };
+struct FuseBwdArgs {
+  const float* dout; const float* out; float* g; float* idst; int iacc;
+  const float* y[3]; double* st[3];
+  long rows; int B, H, W, C, ew0, new_;
+  FuseBwdUp up[3];
+};
+
+// Integer factor F = H / Hs = W / Ws in {2, 4, 8}: the taps of low-res pixel (qy, qx) are the 2F x 2F window starting at
+// (F q - F / 2) (src = (dst + 0.5) / F - 0.5 lies in (q - 1, q + 1) exactly there; clamped borders included).  Thread l of the L
+// that share the pixel takes the RPT = 2F / L rows from row l * RPT of the window, 8 / F rows per round so that 32 loads are in
+// flight (one dependent round trip per round instead of one per row).  Weights by the formula of bilinear_up_bwd_kernel.
+template <int F, class LD>
+__device__ __forceinline__ float fuse_bwd_gather_int(LD ld, int b, int qy, int qx, int c, int H, int W, int C, int Hs, int Ws,
+                                                     int l, int RPT) {
+  constexpr int NX = 2 * F, RU = 8 / F;
+  float wx[NX];
+  unsigned xo[NX];
+#pragma unroll
+  for (int u = 0; u < NX; ++u) {
+    const int x = F * qx - F / 2 + u, xc = min(max(x, 0), W - 1);
+    int x0, x1; float w;
+    bil_src(xc, Ws, W, x0, x1, w);
+    wx[u] = x == xc ? (x0 == qx ? 1.f - w : 0.f) + (x1 == qx ? w : 0.f) : 0.f;
+    xo[u] = (unsigned)(xc * C) * 4u;
+  }
+  const int ys = F * qy - F / 2 + l * RPT;
+  float acc = 0.f;
+  for (int j0 = 0; j0 < RPT; j0 += RU) {
+    float v[RU][NX], cy[RU];
+#pragma unroll
+    for (int jj = 0; jj < RU; ++jj) {
+      const int y = ys + j0 + jj, yc = min(max(y, 0), H - 1);
+      int y0, y1; float w;
+      bil_src(yc, Hs, H, y0, y1, w);
+      cy[jj] = y == yc ? (y0 == qy ? 1.f - w : 0.f) + (y1 == qy ? w : 0.f) : 0.f;
+      const unsigned ro = (unsigned)(((b * H + yc) * W) * C + c) * 4u;
+#pragma unroll
+      for (int u = 0; u < NX; ++u) v[jj][u] = ld(ro + xo[u]);
+    }
+#pragma unroll
+    for (int jj = 0; jj < RU; ++jj) {
+      float part = 0.f;
+#pragma unroll
+      for (int u = 0; u < NX; ++u) part = fmaf(wx[u], v[jj][u], part);
+      acc = fmaf(cy[jj], part, acc);
+    }
+  }
+  return acc;
+}
+
+// Any other ratio: one thread walks the candidate window of bilinear_up_bwd_kernel in its order and association (bit-equal du).
+template <class LD>
+__device__ __forceinline__ float fuse_bwd_gather_any(LD ld, int b, int qy, int qx, int c, int H, int W, int C, int Hs, int Ws) {
+  const float ry = (float)H / (float)Hs, rx = (float)W / (float)Ws;
+  int ylo = (int)floorf(((float)qy - 1.f + 0.5f) * ry - 0.5f) - 1, yhi = (int)ceilf(((float)qy + 1.f + 0.5f) * ry - 0.5f) + 1;
+  int xlo = (int)floorf(((float)qx - 1.f + 0.5f) * rx - 0.5f) - 1, xhi = (int)ceilf(((float)qx + 1.f + 0.5f) * rx - 0.5f) + 1;
+  ylo = max(ylo, 0); yhi = min(yhi, H - 1); xlo = max(xlo, 0); xhi = min(xhi, W - 1);
+  float acc = 0.f;
+  for (int y = ylo; y <= yhi; ++y) {
+    int y0, y1; float wy;
+    bil_src(y, Hs, H, y0, y1, wy);
+    const float cy = (y0 == qy ? 1.f - wy : 0.f) + (y1 == qy ? wy : 0.f);
+    if (cy == 0.f) continue;
+    const unsigned ro = (unsigned)(((b * H + y) * W) * C + c) * 4u;
+    float part = 0.f;
+    for (int xb = xlo; xb <= xhi; xb += 8) {
+      float v[8], wv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int x = min(xb + u, xhi);
+        int x0, x1; float wx;
+        bil_src(x, Ws, W, x0, x1, wx);
+        const float cx = (x0 == qx ? 1.f - wx : 0.f) + (x1 == qx ? wx : 0.f);
+        wv[u] = xb + u <= xhi ? cx : 0.f;
+        v[u] = ld(ro + (unsigned)(x * C) * 4u);
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) part = fmaf(wv[u], v[u], part);
+    }
+    acc = fmaf(cy, part, acc);
+  }
+  return acc;
+}
+
+template <int VW>
+__global__ __launch_bounds__(256) void fuse_sum_bwd_kernel(FuseBwdArgs a) {
+  HRF_DYN_SMEM(float, sacc);
+  const int C = a.C;
+  const float* dout = a.dout;
+  const float* out = a.out;
+  if ((int)blockIdx.x >= a.ew0) {
+    // ---- elementwise section: a thread keeps VW consecutive channels for its whole life (act_bwd_vec_kernel)
+    const int bid = (int)blockIdx.x - a.ew0;
+    float* g = a.g;
+    float* idst = a.idst;
+    const float* y1 = a.y[0];
+    const float* y2 = a.y[1];
+    const float* y3 = a.y[2];
+    double* st1 = a.st[0];
+    double* st2 = a.st[1];
+    double* st3 = a.st[2];
+    const long rows = a.rows;
+    const int cw = C / VW, R = 256 / cw;
+    const int r = threadIdx.x / cw, c = VW * (threadIdx.x - r * cw);
+    const bool active = r < R;
+    float a0[VW], a1[VW], a2[VW], a3[VW];
+#pragma unroll
+    for (int e = 0; e < VW; ++e) a0[e] = a1[e] = a2[e] = a3[e] = 0.f;
+#pragma unroll 2
+    for (long row0 = (long)bid * R; row0 < rows; row0 += (long)a.new_ * R) {
+      const long row = row0 + r;
+      const bool ok = active && row < rows;
+      const long idx = ok ? row * C + c : 0;
+      float v[VW], ov[VW], y1v[VW], y2v[VW], y3v[VW], iv[VW];
+      hrf_ldv<VW>(dout + idx, v);
+      hrf_ldv<VW>(out + idx, ov);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) { y1v[e] = 0.f; y2v[e] = 0.f; y3v[e] = 0.f; iv[e] = 0.f; }
+      if (st1) hrf_ldv<VW>(y1 + idx, y1v);
+      if (st2) hrf_ldv<VW>(y2 + idx, y2v);
+      if (st3) hrf_ldv<VW>(y3 + idx, y3v);
+      if (idst != nullptr && a.iacc) hrf_ldv<VW>(idst + idx, iv);
+#pragma unroll
+      for (int e = 0; e < VW; ++e) {
+        float t = ov[e] > 0.f ? v[e] : 0.f;
+        t = ok ? t : 0.f;
+        v[e] = t;
+        iv[e] = a.iacc ? t + iv[e] : t;
+        a0[e] += t;
+        a1[e] = fmaf(t, y1v[e], a1[e]);
+        a2[e] = fmaf(t, y2v[e], a2[e]);
+        a3[e] = fmaf(t, y3v[e], a3[e]);
+      }
+      if (ok && g != nullptr) hrf_stv<VW>(g + idx, v);
+      if (ok && idst != nullptr) hrf_stv<VW>(idst + idx, iv);
+    }
+    if (st1 == nullptr && st2 == nullptr && st3 == nullptr) return;
+    // [R + 1][4*C]: per row group (sum v, sum v*y1, sum v*y2, sum v*y3) by plain stores, then one pass that adds the R rows
+    if (active) {
+      float* pr = sacc + (size_t)r * 4 * C + c;
+#pragma unroll
+      for (int e = 0; e < VW; ++e) { pr[e] = a0[e]; pr[C + e] = a1[e]; pr[2 * C + e] = a2[e]; pr[3 * C + e] = a3[e]; }
+    }
+    __syncthreads();
+    float* stot = sacc + (size_t)R * 4 * C;
+    for (int i = threadIdx.x; i < 4 * C; i += 256) {
+      float t = 0.f;
+      for (int rr = 0; rr < R; ++rr) t += sacc[(size_t)rr * 4 * C + i];
+      stot[i] = t;
+    }
+    __syncthreads();
+    for (int cc = threadIdx.x; cc < C; cc += 256) {
+      const double s = (double)stot[cc];
+      if (st1) { hrf_stat_add(st1, 2 * C, cc, s); hrf_stat_add(st1, 2 * C, C + cc, (double)stot[C + cc]); }
+      if (st2) { hrf_stat_add(st2, 2 * C, cc, s); hrf_stat_add(st2, 2 * C, C + cc, (double)stot[2 * C + cc]); }
+      if (st3) { hrf_stat_add(st3, 2 * C, cc, s); hrf_stat_add(st3, 2 * C, C + cc, (double)stot[3 * C + cc]); }
+    }
+    return;
+  }
+  // ---- one section per up-sampled term (blk0 ascending; unused terms carry blk0 = the grid size): a thread keeps ONE channel,
+  // Rpix low-res pixels per pass, L threads per (pixel, channel) that share the window rows
+  const int k = (int)blockIdx.x >= a.up[2].blk0 ? 2 : ((int)blockIdx.x >= a.up[1].blk0 ? 1 : 0);
+  const FuseBwdUp u = k == 2 ? a.up[2] : (k == 1 ? a.up[1] : a.up[0]);
+  const int H = a.H, W = a.W, Hs = u.Hs, Ws = u.Ws, L = u.L;
+  const int R = 256 / C, Rpix = R / L, RPT = 2 * u.F / L;
+  const int r = threadIdx.x / C, c = threadIdx.x - r * C;
+  const int slot = r / L, l = r - slot * L;
+  const bool active = slot < Rpix;
+  const int npix = a.B * Hs * Ws;
+  const int bid = (int)blockIdx.x - u.blk0;
+  float* spart = sacc;                                      // [R][C]: the L row shares of every (pixel, channel) of a pass
+  float* smom = sacc + (size_t)R * C;                       // [Rpix][2*C]
+  auto ld = [&](unsigned boff) {
+    const float o = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(out) + boff);
+    const float d = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(dout) + boff);
+    return o > 0.f ? d : 0.f;
+  };
+  float m1 = 0.f, m2 = 0.f;
+  for (int q0 = bid * Rpix; q0 < npix; q0 += u.nblk * Rpix) {
+    const int q = q0 + slot;
+    const bool valid = active && q < npix;
+    float acc = 0.f;
+    if (valid) {
+      const int qx = q % Ws, qy = (q / Ws) % Hs, b = q / (Ws * Hs);
+      if (u.F == 2) acc = fuse_bwd_gather_int<2>(ld, b, qy, qx, c, H, W, C, Hs, Ws, l, RPT);
+      else if (u.F == 4) acc = fuse_bwd_gather_int<4>(ld, b, qy, qx, c, H, W, C, Hs, Ws, l, RPT);
+      else if (u.F == 8) acc = fuse_bwd_gather_int<8>(ld, b, qy, qx, c, H, W, C, Hs, Ws, l, RPT);
+      else acc = fuse_bwd_gather_any(ld, b, qy, qx, c, H, W, C, Hs, Ws);
+    }
+    if (L > 1) {
+      // the L shares meet through plain stores and are added in lane order: the same bits on every run
+      if (active) spart[r * C + c] = acc;
+      __syncthreads();
+      if (valid && l == 0) {
+        acc = 0.f;
+        for (int ll = 0; ll < L; ++ll) acc += spart[(slot * L + ll) * C + c];
+      }
+      __syncthreads();
+    }
+    if (valid && l == 0) {
+      const int i = q * C + c;
+      u.du[i] = acc;
+      m1 += acc;
+      if (u.ylow != nullptr) m2 = fmaf(acc, u.ylow[i], m2);
+    }
+  }
+  if (u.stats == nullptr) return;
+  if (active && l == 0) { smom[(size_t)slot * 2 * C + c] = m1; smom[(size_t)slot * 2 * C + C + c] = m2; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * C; i += 256) {
+    float t = 0.f;
+    for (int rr = 0; rr < Rpix; ++rr) t += smom[(size_t)rr * 2 * C + i];
+    hrf_stat_add(u.stats, 2 * C, i, (double)t);
+  }
+}
+
 
 // out[pix][off + c] = bilinear_up(x)[pix][c]  (align_corners=False; identity copy when Hs == H): the HRFPN
 // concat (hrfpn.py:80-84) written straight into the channel slice of the concatenated row buffer
@@ -1503,7 +1809,10 @@ extern "C" int hrf_fuse_sum(int type0, const float* p0, const float* sc0, const 
     if (a.t[k].type == 4 && (a.t[k].Hs <= 0 || a.t[k].Ws <= 0 || H % a.t[k].Hs || W % a.t[k].Ws)) return HRF_ERR_ARG;
   const long total = (long)B * H * W * C;
   if (total <= 0) return HRF_OK;
-  HRF_LAUNCH_G(fuse_sum_kernel, dim3(ew_grid(total)), dim3(256), 0, stream, a);
+  const int vw = (g_pw_knob[2] == 1 || g_pw_knob[3] == 1) ? 0 : (C % 4 == 0 ? 4 : (C % 2 == 0 ? 2 : 0));   // (hrf_debug_knob 18 / 19 = 1: the per-element kernel)
+  if (vw == 4) { HRF_LAUNCH_G(fuse_sum_vec_kernel<4>, dim3(ew_grid(total / 4)), dim3(256), 0, stream, a); }
+  else if (vw == 2) { HRF_LAUNCH_G(fuse_sum_vec_kernel<2>, dim3(ew_grid(total / 2)), dim3(256), 0, stream, a); }
+  else { HRF_LAUNCH_G(fuse_sum_kernel, dim3(ew_grid(total)), dim3(256), 0, stream, a); }
   return hrf_check_launch();
 }
 
@@ -1531,6 +1840,71 @@ extern "C" int hrf_nearest_up_bwd(const float* g, int ldG, int goff, int B, int 
   if (grid > 1024) grid = 1024;
   HRF_LAUNCH(nearest_up_bwd_kernel, dim3(grid), dim3(256), (size_t)R * 2 * C * sizeof(float), stream, g, ldG, goff,
              B, H, W, C, ylow, Hs, Ws, du, hrf_det_tag(stats));
+  return hrf_check_launch();
+}
+
+extern "C" int hrf_fuse_sum_bwd_supported(int C) { return (C % 2 == 0 && C >= 8 && C <= 256) ? 1 : 0; }
+
+extern "C" int hrf_fuse_sum_bwd(const hrf_fuse_bwd_t* p, void* stream) {
+  if (p == nullptr || p->dout == nullptr || p->out == nullptr || !hrf_fuse_sum_bwd_supported(p->C)) return HRF_ERR_ARG;
+  const int B = p->B, H = p->H, W = p->W, C = p->C;
+  if (B < 1 || H < 1 || W < 1) return HRF_ERR_ARG;
+  FuseBwdArgs a{};
+  a.dout = p->dout; a.out = p->out; a.g = p->g; a.idst = p->id_dst; a.iacc = p->id_accumulate ? 1 : 0;
+  a.rows = (long)B * H * W; a.B = B; a.H = H; a.W = W; a.C = C;
+  bool any_st = false;
+  for (int k = 0; k < 3; ++k) {
+    if (p->st[k] != nullptr && p->y[k] == nullptr) return HRF_ERR_ARG;
+    a.y[k] = p->st[k] != nullptr ? p->y[k] : nullptr;
+    a.st[k] = hrf_det_tag(p->st[k]);
+    any_st = any_st || p->st[k] != nullptr;
+  }
+  if ((long)B * H * W * C >= (1L << 30)) return HRF_ERR_ARG;        // (32-bit byte offsets in the kernel)
+  const int vw = (C % 4 == 0 && C >= 16) ? 4 : 2;
+  const int Rv = 256 / (C / vw);                                   // rows per pass of the elementwise section
+  unsigned smem = any_st ? (unsigned)((Rv + 1) * 4 * C * sizeof(float)) : 0u;
+  const int R = 256 / C;
+  int nu = 0;
+  for (int j = 0; j < 3; ++j) {
+    if (p->up_kind[j] == 0) continue;
+    if (p->up_kind[j] != 1 || p->up_Hs[j] < 1 || p->up_Ws[j] < 1 || p->up_du[j] == nullptr) return HRF_ERR_ARG;
+    if ((long)B * p->up_Hs[j] * p->up_Ws[j] * C >= (1L << 30)) return HRF_ERR_ARG;
+    FuseBwdUp u{};
+    u.ylow = p->up_ylow[j]; u.du = p->up_du[j]; u.stats = hrf_det_tag(p->up_stats[j]); u.Hs = p->up_Hs[j]; u.Ws = p->up_Ws[j];
+    // integer factor 2 / 4 / 8: the 2F window rows of a (pixel, channel) go to L = 1 / 4 / 8 threads (a power of two, as many as
+    // the block's R row groups of C threads allow); any other ratio: one thread walks the window like bilinear_up_bwd_kernel
+    const int f = (H % u.Hs == 0 && W % u.Ws == 0 && H / u.Hs == W / u.Ws) ? H / u.Hs : 0;
+    u.F = (f == 2 || f == 4 || f == 8) ? f : 0;
+    u.L = 1;
+    const int lwant = u.F >= 4 ? u.F : 1;
+    while (u.L * 2 <= lwant && u.L * 2 <= R) u.L *= 2;
+    // sections in the order of their factor, the largest first (any other ratio before them: its threads live longest)
+    int at = nu++;
+    const int key = u.F == 0 ? 99 : u.F;
+    while (at > 0 && (a.up[at - 1].F == 0 ? 99 : a.up[at - 1].F) < key) { a.up[at] = a.up[at - 1]; --at; }
+    a.up[at] = u;
+  }
+  int grid = 0;
+  for (int j = 0; j < nu; ++j) {
+    FuseBwdUp& u = a.up[j];
+    const int Rpix = R / u.L;
+    const long nb = hrf_cdiv((long)B * u.Hs * u.Ws, Rpix);
+    u.nblk = (int)(nb > 1024 ? 1024 : nb);
+    u.blk0 = grid;
+    grid += u.nblk;
+    const unsigned need = (unsigned)(((size_t)R * C + (size_t)Rpix * 2 * C) * sizeof(float));
+    if (need > smem) smem = need;
+  }
+  a.ew0 = grid;
+  if (a.g != nullptr || a.idst != nullptr || any_st) {
+    a.new_ = hrf_cdiv(hrf_cdiv(a.rows, Rv), 4);
+    if (a.new_ > 2048) a.new_ = 2048;
+  }
+  grid += a.new_;
+  for (int j = nu; j < 3; ++j) a.up[j].blk0 = grid;
+  if (grid == 0) return HRF_OK;
+  if (vw == 4) { HRF_LAUNCH(fuse_sum_bwd_kernel<4>, dim3(grid), dim3(256), smem, stream, a); }
+  else { HRF_LAUNCH(fuse_sum_bwd_kernel<2>, dim3(grid), dim3(256), smem, stream, a); }
   return hrf_check_launch();
 }
 

@@ -156,6 +156,13 @@ def work_model(name, a):
     if name == 'hrf_bilinear_up_bwd':
         n = float(a['B']) * a['H'] * a['W'] * a['C']
         return 'bilinear_up_bwd_kernel', 2 * n, f4 * (n + 3.0 * a['B'] * a['Hs'] * a['Ws'] * a['C'])
+    if name == 'hrf_fuse_sum_bwd':
+        # one exchange sum's backward in one launch: flops as for the act_bwd + scale_add + bilinear_up_bwd launches it replaces;
+        # bytes: dout + out + the outputs written (g, identity [+ its old value]) + the y_k read + du written and ylow read
+        n = float(a['B']) * a['H'] * a['W'] * a['C']
+        low = float(a['B']) * a['low_pix'] * a['C']
+        return ('fuse_sum_bwd_kernel', 6 * n + 3 * n * bool(a['has_id']) + 2 * n * a['n_up'],
+                f4 * (n * (2 + a['has_g'] + a['has_id'] + a['n_same']) + 2 * low))
     if name == 'hrf_adamw':
         return 'adamw_kernel', 12.0 * a['n'], f4 * a['n'] * 7
     if name == 'hrf_adamw_clipped':
@@ -198,6 +205,11 @@ class ProfLib:
                         d['w1'] = int(bool(p.w1))
                     if hasattr(p, 'q_out'):                # (hrf_attn_proj_t: a training forward stores q | k | v)
                         d['store'] = int(bool(p.q_out or p.k_out or p.v_out))
+                if hasattr(p, 'up_kind'):                  # hrf_fuse_bwd_t: which sections the launch has
+                    d['n_same'] = sum(1 for k in range(3) if p.st[k])
+                    d['has_g'], d['has_id'] = int(bool(p.g)), int(bool(p.id_dst)) * (1 + int(p.id_accumulate))
+                    ups = [k for k in range(3) if p.up_kind[k]]
+                    d['n_up'], d['low_pix'] = len(ups), sum(p.up_Hs[k] * p.up_Ws[k] for k in ups)
             lv = d.get('lv')
             if isinstance(lv, ctypes.Structure):          # hrf_roi_levels_t: channels, batch and the finest map
                 d['C'], d['B'], d['H'], d['W'], d['HW0'] = lv.C, lv.B, lv.H[0], lv.W[0], lv.H[0] * lv.W[0]

@@ -957,6 +957,7 @@ class Ctx:
         if self.det:
             eng.det_begin()
         self.lin_fused = lin_fused_sites()
+        self.fuse_bwd = fuse_bwd_enabled()
         use_keep_list(self.owner._engine().keep)
         self.owner._engine().fs_prepare()
         # HRF_WGRAD=flush: every time all lanes are joined into the main lane and enough weight gradients are queued,
@@ -2206,6 +2207,62 @@ def materialize(ctx, lazy, act, res=None, lazy2=None, act_first=False, rowscale=
     return out
 
 
+# HRF_FUSE_BWD: the backward of an exchange sum as ONE launch (hrf_fuse_sum_bwd: ReLU mask, identity gradient, moments of the
+# same-resolution terms and every bilinear adjoint as sections of one grid) instead of hrf_act_bwd + hrf_scale_add + one
+# hrf_bilinear_up_bwd per up-sampled term.  0 restores those launches (A/B runs).  Read when a backward pass starts (Ctx.
+# run_backward).  DESIGN 11 has the measurements.
+_FUSE_BWD_DEFAULT = '1'
+
+
+def fuse_bwd_enabled(value=None):
+    v = (os.environ.get('HRF_FUSE_BWD', _FUSE_BWD_DEFAULT) if value is None else value).strip()
+    if v not in ('0', '1'):
+        raise ValueError(f"HRF_FUSE_BWD={v!r}: 0 or 1")
+    return v == '1'
+
+
+def _fuse_sum_bwd_one_launch(ctx, out, dims, terms, same):
+    """Issue hrf_fuse_sum_bwd for this exchange sum -> True; False: a shape or term the kernel refuses (the caller issues the
+    separate launches).  Gradient aliasing is the one of the separate launches: g doubles as st.du of every 'same' term, so
+    it is the identity gradient itself only when no such term exists."""
+    L = ctx.L
+    B, H, W, C = dims
+    on = ctx.__dict__.get('fuse_bwd')
+    if on is None:
+        on = fuse_bwd_enabled()
+    ups = [t for kind, t in terms if kind in ('up', 'near')]
+    ids = [t for kind, t in terms if kind == 'id' and t.needs_grad]
+    if (not on or not hasattr(L, 'hrf_fuse_sum_bwd') or not L.hrf_fuse_sum_bwd_supported(C) or len(ups) > 3 or len(ids) > 1
+            or any(kind == 'near' for kind, _ in terms)):
+        return False
+    p = _lib.FuseBwd()
+    P = _lib._ptr
+    p.dout, p.out, p.B, p.H, p.W, p.C = P(out.grad), P(out.t), B, H, W, C
+    g = None
+    if same or (ids and ids[0].grad is None):
+        g = _new_like(out.t)
+    for k, t in enumerate(same):
+        p.y[k], p.st[k] = P(t.raw), P(t.st.gstats)
+        t.st.du = g
+    if ids:
+        t = ids[0]
+        if t.grad is not None:
+            p.id_dst, p.id_accumulate = P(t.grad), 1
+        elif same:
+            t.grad = _new_like(out.t)
+            p.id_dst = P(t.grad)
+        else:
+            t.grad = g
+    p.g = P(g)
+    for k, t in enumerate(ups):
+        st = t.st
+        st.du = _new_like(st.raw)
+        p.up_kind[k], p.up_ylow[k], p.up_Hs[k], p.up_Ws[k] = 1, P(st.raw), st.raw.shape[1], st.raw.shape[2]
+        p.up_du[k], p.up_stats[k] = P(st.du), P(st.gstats)
+    L.hrf_fuse_sum_bwd(p, ctx.stream)
+    return True
+
+
 def fuse_sum(ctx, dims, terms):
     """HRModule exchange for one output branch: ReLU(sum terms).  terms: list of
     ('id', Act) | ('same', Lazy) | ('up', Lazy: bilinear) | ('near', Lazy: nearest by an integer factor)
@@ -2236,9 +2293,11 @@ def fuse_sum(ctx, dims, terms):
         ctx.probe.append(('out', out.t))
 
     def bwd():
-        g = _new_like(out.t)
         same = [t for kind, t in terms if kind == 'same']
         assert len(same) <= 3
+        if _fuse_sum_bwd_one_launch(ctx, out, dims, terms, same):
+            return
+        g = _new_like(out.t)
         ys = [t.raw for t in same] + [None] * (3 - len(same))
         sts = [t.st.gstats for t in same] + [None] * (3 - len(same))
         L.hrf_act_bwd(out.grad, out.t, ys[0], None, None, None, 1, 0, g, ys[1], ys[2], sts[0], sts[1], sts[2],

@@ -548,6 +548,33 @@ int hrf_bilinear_up_bwd(const float* g, int ldG, int goff, int B, int H, int W, 
 /* adjoint of the nearest up-sampling of term type 4 (block sums) + the same moments                       */
 int hrf_nearest_up_bwd(const float* g, int ldG, int goff, int B, int H, int W, int C, const float* ylow, int Hs, int Ws,
                        float* du, double* stats, void* stream);
+/* The whole backward of ONE exchange sum out = ReLU(sum of terms) in ONE launch: what hrf_act_bwd (mode 0), hrf_scale_add
+ * (the identity term) and one hrf_bilinear_up_bwd per up-sampled term do in series, as block-uniform sections of one grid.
+ * With v = dout * [out > 0] ([B, H, W, C] rows):
+ *   elementwise section: g = v (g nullable: written when a same-resolution term or an aliasing identity needs it);
+ *     id_dst (nullable) = v, or id_dst += v with id_accumulate = 1 (the identity term's gradient);
+ *     same-resolution term k (st[k] != NULL; y[k] its raw conv output): st[k] [HRF_STAT_COPIES][2*C] += (sum v, sum v*y[k]).
+ *   one section per up-sampled term j (up_kind[j] = 1: bilinear, align_corners=False; 0: unused): up_du[j] [B, up_Hs, up_Ws, C]
+ *     = the adjoint of the up-sampling applied to v (read from dout / out with the mask applied on load - no section waits
+ *     for g), up_stats[j] (nullable) += (sum du, sum du*up_ylow[j]) (up_ylow nullable).  For the integer factors 2, 4 and 8
+ *     (H = F up_Hs and W = F up_Ws) the 2F x 2F taps of a (low-resolution pixel, channel) are loaded 32 at a time, their rows
+ *     spread over up to F threads from factor 4 and added in a fixed order; for every other ratio the gather order is the one
+ *     of hrf_bilinear_up_bwd (bit-equal du).
+ * g and id_dst are bit-equal to hrf_act_bwd + hrf_scale_add on the same arguments.  No float atomics on LDS or on the
+ * tensors; the moments go through the replicated / deterministic accumulators like every other entry point.
+ * Taken: C even, 8 <= C <= 256 (hrf_fuse_sum_bwd_supported(C) == 1), up_kind in {0, 1}, every tensor below 2^30 elements.
+ * Everything else - a nearest term included - is HRF_ERR_ARG before any launch: the caller issues the three entry points
+ * above. */
+typedef struct hrf_fuse_bwd {
+  const float* dout; const float* out;
+  int B, H, W, C;
+  float* g;
+  float* id_dst; int id_accumulate;
+  const float* y[3]; double* st[3];
+  int up_kind[3]; const float* up_ylow[3]; int up_Hs[3]; int up_Ws[3]; float* up_du[3]; double* up_stats[3];
+} hrf_fuse_bwd_t;
+int hrf_fuse_sum_bwd_supported(int C);
+int hrf_fuse_sum_bwd(const hrf_fuse_bwd_t* p, void* stream);
 
 /* ---- HRFPN neck pieces (mmdet/models/necks/hrfpn.py:77-100) --------------------
  * hrf_bilinear_up_into: out[pix][off + c] = F.interpolate(x, size=(H,W), mode='bilinear')[pix][c]

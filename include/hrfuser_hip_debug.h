@@ -15,7 +15,8 @@ extern "C" {
  * 1 = its atomics replaced by plain stores (wrong results; 2 = the ci*9+tap variant instead of the tap-blocked one), 2 = the
  * generic weight-gradient kernel, 3 = split cap of the pixel-major kernel, 4 / 6 = the generic implicit-GEMM engine instead of
  * the row-GEMM / 3x3 halo engines, 5 = minimum width of the halo engine's data gradient, 7 = time the grouped weight-gradient
- * launches (hrf_wgrad_group_report), 8 = the LDS-tiled weight gradient (1 = off, 2 = for every stride-1 1x1 problem), 9 = 1: no split over K in the generic forward convolution; 16..19 pointwise.hip, 24..27 conv3w_engine.hip, 28..31 lin2_engine.hip,
+ * launches (hrf_wgrad_group_report), 8 = the LDS-tiled weight gradient (1 = off, 2 = for every stride-1 1x1 problem), 9 = 1: no split over K in the generic forward convolution; 16..19 pointwise.hip (18 = 1: one channel per thread in the
+ * elementwise kernels; 19 = 1: hrf_fuse_sum through its per-element kernel), 24..27 conv3w_engine.hip, 28..31 lin2_engine.hip,
  * 36 = wave-group form of hrf_attn_block_fwd (0 = the dispatcher's choice, 1 / 2 / 4 = that many groups of four waves per window;
  * a launch of a width that is not built for the forced form returns HRF_ERR_ARG), 37 = a QUERY, not a status: returns the form a
  * forward of width `value` takes now (0: the forced form is not built for it). */
