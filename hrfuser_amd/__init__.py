@@ -14,6 +14,9 @@ from .neck import HRFPN, build_neck                        # noqa: F401,E402
 from .pipeline import DeviceInputPipeline                  # noqa: F401,E402
 from .registry import ROI_EXTRACTORS                       # noqa: F401,E402
 from .roi import SingleRoIExtractor, roi_align, build_roi_extractor   # noqa: F401,E402
+from .registry import HEADS                                # noqa: F401,E402
+from .rpn import RPNHead, build_head                       # noqa: F401,E402
 
 __all__ = ['BACKBONES', 'NECKS', 'build_backbone', 'build_neck', 'HRFuserHRFormerBased', 'HRFuserHRNetBased', 'HRFormer', 'HRFPN',
-           'ROI_EXTRACTORS', 'SingleRoIExtractor', 'roi_align', 'build_roi_extractor']
+           'ROI_EXTRACTORS', 'SingleRoIExtractor', 'roi_align', 'build_roi_extractor',
+           'HEADS', 'RPNHead', 'build_head']

@@ -2106,3 +2106,6 @@ extern "C" int hrf_memset(void* ptr, int value, long bytes, void* stream) {
 
 // multi-level RoIAlign (SingleRoIExtractor) forward / backward: hrf_roi_align_fwd / _bwd
 #include "hrf_roi.h"
+
+// RPN proposal generation (top-k + decode, per-level NMS, merge): hrf_rpn_select_decode / hrf_nms_segments / hrf_rpn_proposals
+#include "hrf_rpn.h"

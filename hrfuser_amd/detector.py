@@ -13,7 +13,7 @@ import torch.nn as nn
 
 from . import _lib
 from . import runtime as R
-from .registry import BACKBONES, NECKS, ROI_EXTRACTORS
+from .registry import BACKBONES, HEADS, NECKS, ROI_EXTRACTORS
 from .trainer import Trainer
 
 
@@ -25,9 +25,10 @@ def combine_mod_imgs(lidar_img=None, radar_img=None, gated_img=None):
 
 class FeatureExtractor(nn.Module):
     """backbone (+ neck) of a `TwoStageDetector` config: `FeatureExtractor(cfg.model.backbone, cfg.model.neck)`;
-    `bbox_roi_extractor` (optional): the `roi_head.bbox_roi_extractor` dict of the config (hrfuser_amd.roi)."""
+    `bbox_roi_extractor` (optional): the `roi_head.bbox_roi_extractor` dict of the config (hrfuser_amd.roi); `rpn_head`
+    (optional): the `rpn_head` dict of the config plus `test_cfg=cfg.model.test_cfg.rpn` (hrfuser_amd.rpn)."""
 
-    def __init__(self, backbone, neck=None, bbox_roi_extractor=None):
+    def __init__(self, backbone, neck=None, bbox_roi_extractor=None, rpn_head=None):
         super().__init__()
         self.backbone = BACKBONES.build(backbone) if isinstance(backbone, dict) else backbone      # two_stage.py:41
         if neck is not None:
@@ -35,6 +36,8 @@ class FeatureExtractor(nn.Module):
         if bbox_roi_extractor is not None:                                                          # standard_roi_head.py:25
             self.bbox_roi_extractor = (ROI_EXTRACTORS.build(bbox_roi_extractor) if isinstance(bbox_roi_extractor, dict)
                                        else bbox_roi_extractor)
+        if rpn_head is not None:                                                                    # two_stage.py:46-50
+            self.rpn_head = HEADS.build(rpn_head) if isinstance(rpn_head, dict) else rpn_head
 
     @property
     def with_neck(self):
@@ -61,12 +64,29 @@ class FeatureExtractor(nn.Module):
             x = self.neck(x)
         return x
 
-    def extract_roi_feats(self, img, rois, lidar_img=None, radar_img=None, gated_img=None):
+    def _proposals(self, x, img, img_shapes, cfg):
+        if getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor: built without an rpn_head')
+        if img_shapes is None:
+            img_shapes = [tuple(img.shape[-2:])] * img.shape[0]
+        return self.rpn_head.proposals(*self.rpn_head(x), img_shapes, cfg)
+
+    def extract_proposals(self, img, img_shapes=None, lidar_img=None, radar_img=None, gated_img=None, cfg=None):
+        """extract_feat followed by the RPN head (two_stage.py:178-181 `rpn_head.simple_test_rpn(x, img_metas)`, with fixed
+        shapes): -> (dets (B,max_per_img,5), count (B,) int32, rois (B*max_per_img,5)), no synchronisation.  img_shapes: (B,2)
+        device tensor or list of (h, w[, c]); None: the padded input size."""
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        return self._proposals(x, img, img_shapes, cfg)
+
+    def extract_roi_feats(self, img, rois=None, lidar_img=None, radar_img=None, gated_img=None, img_shapes=None):
         """extract_feat followed by the RoI extractor (standard_roi_head.py:116-118: `bbox_roi_extractor(x[:num_inputs],
-        rois)`): rois (K,5) = (batch index, x1, y1, x2, y2) -> (K, out_channels, 7, 7)."""
+        rois)`): rois (K,5) = (batch index, x1, y1, x2, y2) -> (K, out_channels, 7, 7).  rois None: the `rois` of the RPN head
+        (B * max_per_img rows, the padded ones give rows of zeros)."""
         if getattr(self, 'bbox_roi_extractor', None) is None:
             raise ValueError('FeatureExtractor.extract_roi_feats: built without a bbox_roi_extractor')
         x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        if rois is None:
+            rois = self._proposals(x, img, img_shapes, None)[2]
         return self.bbox_roi_extractor(x, rois)
 
     def forward(self, img, lidar_img=None, radar_img=None, gated_img=None):

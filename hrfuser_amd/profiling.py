@@ -128,6 +128,14 @@ def work_model(name, a):
         fp = K * min(23.0 * 23.0, float(a.get('HW0', 23 * 23))) * C
         fl = 2.0 * K * 49 * C * 4 * 4                     # ~2 x 2 samples of 4 corners per bin
         return ('roi_align_fwd_kernel' if name.endswith('fwd') else 'roi_align_bwd_kernel'), fl, f4 * (fp + K * 49 * C)
+    if name in ('hrf_rpn_select_decode', 'hrf_rpn_proposals'):
+        # RPN proposals, priced by the traffic of stage 1 (the select reads every logit about five times: four radix passes and the
+        # compaction; deltas and candidate rows only for the nms_pre winners per level); the NMS stages move a data-dependent part
+        # of the n x n / 64 bit matrices and are not priced - tools/rpn_proposals_cost.py times them
+        n = float(a['B']) * a['anchors']
+        return ('rpn_select_decode_kernel' if name.endswith('decode') else 'rpn_proposals (4 kernels)'), 0.0, f4 * 5.0 * n
+    if name == 'hrf_nms_segments':
+        return 'rpn_nms (3 kernels)', 0.0, 0.0
     if name == 'hrf_conv3_packed_bf16x3':
         # bf16x3 matrix mode of the wide 3x3 engine: the algorithmic work of the convolution (one multiply-add per term, whatever
         # the three split products cost - MFMA_ROOF prices those) and its fp32 rows and pack
@@ -211,7 +219,12 @@ class ProfLib:
                     ups = [k for k in range(3) if p.up_kind[k]]
                     d['n_up'], d['low_pix'] = len(ups), sum(p.up_Hs[k] * p.up_Ws[k] for k in ups)
             lv = d.get('lv')
-            if isinstance(lv, ctypes.Structure):          # hrf_roi_levels_t: channels, batch and the finest map
+            if isinstance(lv, ctypes.Structure) and hasattr(lv, 'ld_cls'):   # hrf_rpn_levels_t: batch, the finest map, all anchors of an image
+                d['B'], d['H'], d['W'], d['A'] = lv.B, lv.H[0], lv.W[0], lv.A
+                d['anchors'] = sum(lv.H[l] * lv.W[l] for l in range(lv.num_levels)) * lv.A
+                cfg = d.get('cfg')
+                d['nms_pre'] = cfg.nms_pre if isinstance(cfg, ctypes.Structure) else 0
+            elif isinstance(lv, ctypes.Structure):        # hrf_roi_levels_t: channels, batch and the finest map
                 d['C'], d['B'], d['H'], d['W'], d['HW0'] = lv.C, lv.B, lv.H[0], lv.W[0], lv.H[0] * lv.W[0]
             return d
 

@@ -64,6 +64,7 @@ BACKBONES, USING_MMDET = _resolve()
 MODELS = BACKBONES
 NECKS = MODELS            # mmdet 2.19: BACKBONES = NECKS = ... = MODELS (mmdet/models/builder.py:7-15)
 ROI_EXTRACTORS = MODELS   # (the same alias: builder.py:11)
+HEADS = MODELS            # (the same alias: builder.py:13)
 
 
 def build_backbone(cfg):

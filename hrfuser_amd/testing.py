@@ -110,3 +110,128 @@ def roi_extract_ref(feats, rois, strides, finest_scale=56, levels=None, P=7):
             ss = float(torch.tensor(1.0 / strides[l], dtype=torch.float32))
             out = out.index_add(0, sel, roi_align_ref(feats[l], rois[sel], ss, P))
     return out
+
+
+# ----------------------------------------------------------------------------- RPNHead.get_bboxes restatement
+# The oracle of hrfuser_amd.rpn / csrc/hrf_rpn.h (no mmcv here: parity against real mmcv nms is unpinned): a
+# literal fp32 torch restatement of rpn_head.py:103-235 with anchor_generator.py:151-194 / 241-281, delta_xywh_bbox_coder.py:
+# 164-260 and mmcv 1.3.17 nms (offset 0), every stage callable on its own.  Where the reference leaves the result open or
+# non-finite the restatement fixes it as the header states: equal scores go to the lower index (a stable sort), a NaN logit
+# ranks last and its candidate is invalid, levels are separate NMS problems (no coordinate offset).
+def rpn_base_anchors(base_size, scales, ratios, center_offset=0.0):
+    """gen_single_level_base_anchors (anchor_generator.py:151-194, scale_major) -> (len(ratios) * len(scales), 4) fp32"""
+    scales, ratios = torch.tensor(scales, dtype=torch.float32), torch.tensor(ratios, dtype=torch.float32)
+    w = h = base_size
+    xc, yc = center_offset * w, center_offset * h
+    h_ratios = torch.sqrt(ratios)
+    w_ratios = 1 / h_ratios
+    ws = (w * w_ratios[:, None] * scales[None, :]).view(-1)
+    hs = (h * h_ratios[:, None] * scales[None, :]).view(-1)
+    return torch.stack([xc - 0.5 * ws, yc - 0.5 * hs, xc + 0.5 * ws, yc + 0.5 * hs], dim=-1)
+
+
+def rpn_grid_anchors(base, H, W, stride):
+    """single_level_grid_priors (anchor_generator.py:241-281) -> (H * W * A, 4) fp32, row (y * W + x) * A + a"""
+    sx = torch.arange(0, W).to(torch.float32) * stride
+    sy = torch.arange(0, H).to(torch.float32) * stride
+    xx, yy = sx.repeat(H), sy.view(-1, 1).repeat(1, W).view(-1)
+    shifts = torch.stack([xx, yy, xx, yy], dim=-1)
+    return (base[None, :, :] + shifts[:, None, :]).view(-1, 4)
+
+
+def rpn_delta2bbox(rois, deltas, max_shape=None, wh_ratio_clip=16 / 1000):
+    """delta2bbox (delta_xywh_bbox_coder.py:224-260) with means 0, stds 1, clip_border -> (N, 4), the dtype of the inputs"""
+    import math
+    dxy, dwh = deltas[:, :2], deltas[:, 2:]
+    pxy = (rois[:, :2] + rois[:, 2:]) * 0.5
+    pwh = rois[:, 2:] - rois[:, :2]
+    dxy_wh = pwh * dxy
+    max_ratio = abs(math.log(wh_ratio_clip))
+    dwh = dwh.clamp(min=-max_ratio, max=max_ratio)
+    gxy = pxy + dxy_wh
+    gwh = pwh * dwh.exp()
+    boxes = torch.cat([gxy - gwh * 0.5, gxy + gwh * 0.5], dim=-1)
+    if max_shape is not None:
+        boxes[:, 0::2].clamp_(min=0, max=float(max_shape[1]))
+        boxes[:, 1::2].clamp_(min=0, max=float(max_shape[0]))
+    return boxes
+
+
+def rpn_rank(logits, k, by='logit'):
+    """the k first indices of a stable descending sort of the flat logits (by='sigmoid': of their fp32 sigmoid, what the
+    reference sorts); NaN last"""
+    v = logits if by == 'logit' else logits.sigmoid()
+    nan = torch.isnan(v)
+    order = torch.argsort(torch.where(nan, torch.full_like(v, float('-inf')), v), descending=True, stable=True)
+    order = torch.cat([order[~nan[order]], order[nan[order]]])
+    return order[:k]
+
+
+def rpn_stage1_ref(cls_scores, bbox_preds, img_shapes, strides, bases, nms_pre, min_bbox_size=0.0, by='logit'):
+    """cls_scores[l] (B,A,H,W), bbox_preds[l] (B,4A,H,W) fp32 CPU, img_shapes [(h, w)], bases[l] (A,4) ->
+    out[b][l] = dict(idx (k,) int64, cand (k,5) = box + logit, valid (k,) bool): rpn_head.py:150-187 + :217-228"""
+    out = []
+    for b in range(cls_scores[0].shape[0]):
+        levels = []
+        for l, (cs, bp) in enumerate(zip(cls_scores, bbox_preds)):
+            H, W = cs.shape[-2:]
+            logit = cs[b].float().permute(1, 2, 0).reshape(-1)
+            deltas = bp[b].float().permute(1, 2, 0).reshape(-1, 4)
+            idx = rpn_rank(logit, min(nms_pre, logit.numel()), by)
+            anchors = rpn_grid_anchors(bases[l], H, W, strides[l])[idx]
+            boxes = rpn_delta2bbox(anchors, deltas[idx], max_shape=img_shapes[b])
+            w, h = boxes[:, 2] - boxes[:, 0], boxes[:, 3] - boxes[:, 1]
+            valid = (w > min_bbox_size) & (h > min_bbox_size) & ~torch.isnan(logit[idx])
+            levels.append(dict(idx=idx, cand=torch.cat([boxes, logit[idx, None]], dim=1), valid=valid))
+        out.append(levels)
+    return out
+
+
+def nms_iou(boxes):
+    """pairwise IoU (n, n) in the dtype of `boxes`, in the order mmcv's kernel writes it (offset 0)"""
+    x1, y1, x2, y2 = boxes[:, 0], boxes[:, 1], boxes[:, 2], boxes[:, 3]
+    area = (x2 - x1) * (y2 - y1)
+    iw = (torch.min(x2[:, None], x2[None, :]) - torch.max(x1[:, None], x1[None, :])).clamp(min=0)
+    ih = (torch.min(y2[:, None], y2[None, :]) - torch.max(y1[:, None], y1[None, :])).clamp(min=0)
+    inter = iw * ih
+    return inter / (area[:, None] + area[None, :] - inter)
+
+
+def nms_greedy_ref(boxes, valid, thr):
+    """greedy NMS in row order on fp32 boxes -> keep (n,) bool; invalid rows are never kept and suppress nothing"""
+    n = boxes.shape[0]
+    keep = torch.zeros(n, dtype=torch.bool)
+    if n == 0:
+        return keep
+    over = nms_iou(boxes.float()) > thr
+    dead = ~valid.clone() if valid is not None else torch.zeros(n, dtype=torch.bool)
+    for i in range(n):
+        if dead[i]:
+            continue
+        keep[i] = True
+        dead[i + 1:] |= over[i, i + 1:]
+    return keep
+
+
+def nms_segments_ref(segs, thr, max_per_img, sigmoid=True):
+    """segs = [dict(cand (n,5), valid (n,) or None)] of ONE image, each in descending score order -> (dets (m,5) fp32,
+    src (m,2) int64 = (segment, row) of every output row): per-segment greedy NMS, then a stable descending sort of the kept
+    scores over the concatenation (ties: lower segment, lower row), [:max_per_img]"""
+    rows, src = [], []
+    for s, sg in enumerate(segs):
+        keep = nms_greedy_ref(sg['cand'][:, :4], sg.get('valid'), thr)
+        sel = torch.nonzero(keep)[:, 0]
+        rows.append(sg['cand'][sel])
+        src.append(torch.stack([torch.full_like(sel, s), sel], dim=1))
+    rows, src = torch.cat(rows), torch.cat(src)
+    order = torch.argsort(rows[:, 4], descending=True, stable=True)[:max_per_img]
+    dets = rows[order].clone()
+    if sigmoid:
+        dets[:, 4] = dets[:, 4].sigmoid()
+    return dets, src[order]
+
+
+def rpn_proposals_ref(cls_scores, bbox_preds, img_shapes, strides, bases, nms_pre, max_per_img, iou_thr=0.7, min_bbox_size=0.0):
+    """RPNHead.get_bboxes -> [(n_b, 5)] per image: (x1, y1, x2, y2, score)"""
+    st1 = rpn_stage1_ref(cls_scores, bbox_preds, img_shapes, strides, bases, nms_pre, min_bbox_size)
+    return [nms_segments_ref(levels, iou_thr, max_per_img)[0] for levels in st1]

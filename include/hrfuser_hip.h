@@ -424,6 +424,73 @@ typedef struct hrf_roi_levels {
 int hrf_roi_align_supported(int C, int pooled, int num_levels);
 int hrf_roi_align_fwd(const hrf_roi_levels_t* lv, const float* rois, int K, float* out, int out_layout, void* stream);
 int hrf_roi_align_bwd(const hrf_roi_levels_t* lv, const float* rois, int K, const float* dout, int out_layout, void* stream);
+
+/* ---- RPN proposal generation: top-k + decode, per-level NMS, merge (csrc/hrf_rpn.h, part of csrc/pointwise.hip) ------------
+ * The producer of the `rois` above: what RPNHead.get_bboxes does at test time with the head's two maps per level
+ * (mmdet/models/dense_heads/base_dense_head.py:32-108, rpn_head.py:103-235, anchor_generator.py:241-281,
+ * delta_xywh_bbox_coder.py:164-260 with means 0 / stds 1, mmcv 1.3.17 batched_nms with the level as the class id), as FOUR
+ * launches with fixed-shape outputs: no host read of an input, no allocation, no synchronisation, no float atomics (the same
+ * bits in deterministic mode), every loop bounded by a map size or HRF_RPN_MAX_PRE - capturable in a hipGraph.  Logits and
+ * deltas are unvalidated device data and may be NaN / Inf.
+ *   cls[l]     objectness logits (use_sigmoid: one per anchor), NHWC fp32 [B][H_l][W_l] rows of pitch ld_cls_l >= A floats;
+ *   reg[l]     deltas (dx, dy, dw, dh) per anchor, NHWC fp32 [B][H_l][W_l] rows of pitch ld_reg_l >= 4 A floats;
+ *              the flat anchor index of a level is (y * W + x) * A + a, the order of permute(1, 2, 0).reshape(-1);
+ *   stride[l]  anchor stride of the level; base_anchors[(l * HRF_RPN_MAX_ANCHORS + a) * 4 ..] = (x1, y1, x2, y2) of base anchor a
+ *              (AnchorGenerator.gen_single_level_base_anchors, computed by the caller); anchor = base + (x, y, x, y) * stride;
+ *   img_shape  [B][2] fp32 on the device: (height, width) every box of image b is clipped to; read at run time - a captured
+ *              graph follows a changed array;
+ *   cfg        nms_pre (1 .. HRF_RPN_MAX_PRE), max_per_img (>= 1), iou_thr in (0, 1], min_bbox_size >= 0.
+ * Stage 1 (hrf_rpn_select_decode), per (image, level): the k_l = min(nms_pre, H_l W_l A) anchors of largest RAW logit in
+ * descending order - sigmoid is monotone; equal logits: lower flat index first; -0 == +0; a NaN logit ranks below every number -
+ * are decoded (delta2bbox in its written fp32 order, dw / dh clamped to +-|log(16 / 1000)|, clipped to the image) into
+ *   cand       [B][K][5] fp32, K = sum_l k_l, level l of image b at rows b * K + sum_{j<l} k_j ..: (x1, y1, x2, y2, logit);
+ *   valid      [B][K] int32: 1 when w > min_bbox_size && h > min_bbox_size (a NaN box fails) and the logit is not NaN
+ *              (DEVIATION: the reference keeps a NaN score); idx (nullable) [B][K] int32: the flat anchor index of each row.
+ * Stages 2 + 3 (hrf_nms_segments, usable for any per-segment NMS): `cand` / `valid` (nullable: all valid) as above for nseg
+ * segments per image of seg_len[s] rows (a HOST array, 0 <= seg_len[s] <= HRF_RPN_MAX_PRE, nseg <= HRF_RPN_MAX_LEVELS), every
+ * segment in descending score order (the merge relies on it).  Greedy NMS in row order within a segment: row j is dropped when an
+ * earlier KEPT row i has iou > iou_thr, with area = (x2-x1)*(y2-y1), iw = max(min(x2i,x2j) - max(x1i,x1j), 0), ih likewise,
+ * inter = iw*ih, iou = inter / (area_i + area_j - inter) in fp32 in exactly this order; invalid rows are never kept and
+ * suppress nothing; segments are independent (mmcv's coordinate-offset form of that is not reproduced).  The kept rows of an
+ * image are ordered by score descending - ties: lower segment, then lower row - and the first max_per_img become
+ *   dets       [B][max_per_img][5] fp32 (x1, y1, x2, y2, apply_sigmoid ? 1 / (1 + exp(-score)) : score), rows past count[b] zero;
+ *   count      [B] int32;
+ *   rois       [B * max_per_img][5] fp32 (b, x1, y1, x2, y2) - bbox2roi's layout, hrf_roi_align_fwd's input - padded rows
+ *              (b, 0, 0, 0, 0) (RoIAlign gives them a row of zeros).
+ *   workspace  caller-owned device memory of hrf_nms_workspace_bytes / hrf_rpn_workspace_bytes bytes, 256-byte aligned, contents
+ *              irrelevant (suppression bit matrices, keep words, counts; for hrf_rpn_proposals also cand / valid).
+ * hrf_rpn_proposals = all three on the sigmoid of the logit.  hrf_rpn_supported -> 1 / 0; the *_workspace_bytes return 0 for
+ * what is refused.  REFUSED with HRF_ERR_ARG before any launch: nms_pre outside [1, HRF_RPN_MAX_PRE], A outside
+ * [1, HRF_RPN_MAX_ANCHORS], num_levels outside [1, HRF_RPN_MAX_LEVELS], a null map or output, H / W / stride / B < 1, a pitch
+ * smaller than the row, max_per_img < 1, iou_thr outside (0, 1], a negative min_bbox_size, a workspace that is too small.    */
+#define HRF_RPN_MAX_LEVELS 5
+#define HRF_RPN_MAX_ANCHORS 3
+#define HRF_RPN_MAX_PRE 2048
+#define HRF_RPN_ANCHOR_FLOATS 60               /* HRF_RPN_MAX_LEVELS * HRF_RPN_MAX_ANCHORS * 4 */
+typedef struct hrf_rpn_levels {
+  int num_levels, A, B;
+  const float* cls[HRF_RPN_MAX_LEVELS];
+  const float* reg[HRF_RPN_MAX_LEVELS];
+  int H[HRF_RPN_MAX_LEVELS];
+  int W[HRF_RPN_MAX_LEVELS];
+  int ld_cls[HRF_RPN_MAX_LEVELS];
+  int ld_reg[HRF_RPN_MAX_LEVELS];
+  int stride[HRF_RPN_MAX_LEVELS];
+  float base_anchors[HRF_RPN_ANCHOR_FLOATS];
+} hrf_rpn_levels_t;
+typedef struct hrf_rpn_cfg {
+  int nms_pre, max_per_img;
+  float iou_thr, min_bbox_size;
+} hrf_rpn_cfg_t;
+int hrf_rpn_supported(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg);
+long hrf_rpn_workspace_bytes(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg);
+long hrf_nms_workspace_bytes(const int* seg_len, int nseg, int B);
+int hrf_rpn_select_decode(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, const float* img_shape, float* cand, int* valid,
+                          int* idx, void* stream);
+int hrf_nms_segments(const float* cand, const int* valid, const int* seg_len, int nseg, int B, int max_per_img, float iou_thr,
+                     int apply_sigmoid, void* workspace, long workspace_bytes, float* dets, int* count, float* rois, void* stream);
+int hrf_rpn_proposals(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, const float* img_shape, void* workspace,
+                      long workspace_bytes, float* dets, int* count, float* rois, void* stream);
 /* the same gather for EVERY fused layer of a step in one launch: seg = nseg rows of 5 longs on the device {offset (floats) of the
  * layer's ds_plane in `planes`, windows, heads, address of its drpb accumulator, copy_stride}; max_nwin / max_heads = the
  * largest of the rows (launch geometry).                                                                               */
