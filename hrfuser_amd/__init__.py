@@ -16,7 +16,8 @@ from .registry import ROI_EXTRACTORS                       # noqa: F401,E402
 from .roi import SingleRoIExtractor, roi_align, build_roi_extractor   # noqa: F401,E402
 from .registry import HEADS                                # noqa: F401,E402
 from .rpn import RPNHead, build_head                       # noqa: F401,E402
+from .roi_head import CascadeRoIHead, Shared2FCBBoxHead    # noqa: F401,E402
 
 __all__ = ['BACKBONES', 'NECKS', 'build_backbone', 'build_neck', 'HRFuserHRFormerBased', 'HRFuserHRNetBased', 'HRFormer', 'HRFPN',
            'ROI_EXTRACTORS', 'SingleRoIExtractor', 'roi_align', 'build_roi_extractor',
-           'HEADS', 'RPNHead', 'build_head']
+           'HEADS', 'RPNHead', 'build_head', 'CascadeRoIHead', 'Shared2FCBBoxHead']

@@ -970,3 +970,5 @@ extern "C" __attribute__((visibility("hidden"))) int hrf_conv3w_knob(int key, in
   if (key == 2) { g_wsplit = value; return HRF_OK; }
   return HRF_ERR_ARG;
 }
+
+#include "hrf_fc.h"

@@ -52,16 +52,23 @@ constexpr int RPN_WORDS = HRF_RPN_MAX_PRE / 64;        // 64-candidate blocks of
 constexpr int RPN_PREF = RPN_WORDS + 1;        // prefix counts per segment (the last one: the segment's total)
 typedef unsigned long long rpn_u64;
 
+#define RPN_SEL(arr, l) ((l) == 0 ? (arr)[0] : (l) == 1 ? (arr)[1] : (l) == 2 ? (arr)[2] : (l) == 3 ? (arr)[3] : (arr)[4])
+
+// SEG_SEL: entry l of a segment table's member.  The NMS kernels are templates over the table SG: RpnSegs (below: arrays of
+// HRF_RPN_MAX_LEVELS entries, picked with selects so that the by-value kernel argument stays in registers) or a `uniform` table
+// whose members are indexable objects (hrf_bbox.h: up to HRF_BBOX_MAX_CLASSES segments of one length).  SG::uniform is a
+// constant: the other arm folds away.
+#define SEG_SEL(SG, sg, arr, l) (SG::uniform ? (sg).arr[l] : RPN_SEL((sg).arr, l))
+
 // the segments of ONE image (every image has the same): rows of `cand`, words of the suppression matrices
 struct RpnSegs {
+  static constexpr bool uniform = false;
   int nseg, ktot;
   int n[HRF_RPN_MAX_LEVELS];                   // candidates
   int off[HRF_RPN_MAX_LEVELS];                 // first row within the image
   long moff[HRF_RPN_MAX_LEVELS];               // first matrix word within the image
   long mtot;                                   // matrix words of one image
 };
-
-#define RPN_SEL(arr, l) ((l) == 0 ? (arr)[0] : (l) == 1 ? (arr)[1] : (l) == 2 ? (arr)[2] : (l) == 3 ? (arr)[3] : (arr)[4])
 
 // order-preserving integer image of a logit: a > b  <=>  key(a) > key(b); -0 == +0; NaN -> 0, below every number
 __device__ __forceinline__ unsigned rpn_key(float f) {
@@ -183,13 +190,14 @@ __global__ __launch_bounds__(RPN_NT) void rpn_select_decode_kernel(hrf_rpn_level
   }
 }
 
-__global__ __launch_bounds__(64) void rpn_nms_tile_kernel(const float* cand, RpnSegs sg, float thr, rpn_u64* mask) {
+template <class SG>
+__global__ __launch_bounds__(64) void rpn_nms_tile_kernel(const float* cand, SG sg, float thr, rpn_u64* mask) {
   __shared__ float s_box[64][5];
   const int b = blockIdx.z / sg.nseg, s = blockIdx.z - b * sg.nseg, t = threadIdx.x;
-  const int n = RPN_SEL(sg.n, s), nb = (n + 63) >> 6;
+  const int n = SEG_SEL(SG, sg, n, s), nb = (n + 63) >> 6;
   const int ib = blockIdx.y, jb = blockIdx.x;
   if (ib > jb || jb >= nb) return;             // (block-uniform)
-  const float* base = cand + ((long)b * sg.ktot + RPN_SEL(sg.off, s)) * 5;
+  const float* base = cand + ((long)b * sg.ktot + SEG_SEL(SG, sg, off, s)) * 5;
   const int j0 = jb * 64;
   {
     float v[4] = {0.f, 0.f, 0.f, 0.f};
@@ -213,16 +221,17 @@ __global__ __launch_bounds__(64) void rpn_nms_tile_kernel(const float* cand, Rpn
     const float iou = inter / (area + s_box[jj][4] - inter);
     if (iou > thr) bits |= 1ull << jj;
   }
-  mask[(long)b * sg.mtot + RPN_SEL(sg.moff, s) + (long)i * nb + jb] = bits;
+  mask[(long)b * sg.mtot + SEG_SEL(SG, sg, moff, s) + (long)i * nb + jb] = bits;
 }
 
-__global__ __launch_bounds__(64) void rpn_nms_reduce_kernel(const int* valid, RpnSegs sg, const rpn_u64* mask, rpn_u64* keepw, int* pref) {
+template <class SG>
+__global__ __launch_bounds__(64) void rpn_nms_reduce_kernel(const int* valid, SG sg, const rpn_u64* mask, rpn_u64* keepw, int* pref) {
   __shared__ rpn_u64 s_d[64];
   __shared__ int s_pc[64];
   const int b = blockIdx.x / sg.nseg, s = blockIdx.x - b * sg.nseg, lane = threadIdx.x;
-  const int n = RPN_SEL(sg.n, s), nb = (n + 63) >> 6;
-  const long row0 = (long)b * sg.ktot + RPN_SEL(sg.off, s);
-  const rpn_u64* M = mask + (long)b * sg.mtot + RPN_SEL(sg.moff, s);
+  const int n = SEG_SEL(SG, sg, n, s), nb = (n + 63) >> 6;
+  const long row0 = (long)b * sg.ktot + SEG_SEL(SG, sg, off, s);
+  const rpn_u64* M = mask + (long)b * sg.mtot + SEG_SEL(SG, sg, moff, s);
   rpn_u64 removed = ~0ull;
   if (lane < nb) {
     removed = 0ull;
@@ -269,8 +278,10 @@ __device__ __forceinline__ int rpn_kept_before(const rpn_u64* keepw, const int* 
   return pref[w] + (bit ? rpn_popc(keepw[w] & ((1ull << bit) - 1ull)) : 0);
 }
 
-__global__ __launch_bounds__(256) void rpn_merge_kernel(const float* cand, RpnSegs sg, const rpn_u64* keepw, const int* pref, int maxp,
-                                                        int sigmoid, float* dets, int* count, float* rois) {
+// rois / labels are nullable; labels[b][rank] = the segment of the row, -1 past the count
+template <class SG>
+__global__ __launch_bounds__(256) void rpn_merge_kernel(const float* cand, SG sg, const rpn_u64* keepw, const int* pref, int maxp,
+                                                        int sigmoid, float* dets, int* count, float* rois, int* labels) {
   const int b = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
   const rpn_u64* kw = keepw + (long)b * sg.nseg * RPN_WORDS;
   const int* pf = pref + (long)b * sg.nseg * RPN_PREF;
@@ -280,14 +291,18 @@ __global__ __launch_bounds__(256) void rpn_merge_kernel(const float* cand, RpnSe
   if (j == 0) count[b] = cnt;
   if (j < maxp && j >= cnt) {
     float* d = dets + ((long)b * maxp + j) * 5;
-    float* r = rois + ((long)b * maxp + j) * 5;
-    for (int c = 0; c < 5; ++c) { d[c] = 0.f; r[c] = c == 0 ? (float)b : 0.f; }
+    for (int c = 0; c < 5; ++c) d[c] = 0.f;
+    if (rois != nullptr) {
+      float* r = rois + ((long)b * maxp + j) * 5;
+      for (int c = 0; c < 5; ++c) r[c] = c == 0 ? (float)b : 0.f;
+    }
+    if (labels != nullptr) labels[(long)b * maxp + j] = -1;
   }
   if (j >= sg.ktot) return;
   int s = 0;
-  while (s + 1 < sg.nseg && j >= RPN_SEL(sg.off, s) + RPN_SEL(sg.n, s)) ++s;
-  const int r = j - RPN_SEL(sg.off, s);
-  if (r >= RPN_SEL(sg.n, s)) return;
+  while (s + 1 < sg.nseg && j >= SEG_SEL(SG, sg, off, s) + SEG_SEL(SG, sg, n, s)) ++s;
+  const int r = j - SEG_SEL(SG, sg, off, s);
+  if (r >= SEG_SEL(SG, sg, n, s)) return;
   if (!((kw[s * RPN_WORDS + (r >> 6)] >> (r & 63)) & 1ull)) return;
   const float* img = cand + (long)b * sg.ktot * 5;
   const float* me = img + (long)j * 5;
@@ -295,8 +310,8 @@ __global__ __launch_bounds__(256) void rpn_merge_kernel(const float* cand, RpnSe
   int rank = rpn_kept_before(kw + s * RPN_WORDS, pf + s * RPN_PREF, r);
   for (int s2 = 0; s2 < sg.nseg; ++s2) {
     if (s2 == s) continue;
-    const float* other = img + (long)RPN_SEL(sg.off, s2) * 5 + 4;
-    int lo = 0, hi = RPN_SEL(sg.n, s2);
+    const float* other = img + (long)SEG_SEL(SG, sg, off, s2) * 5 + 4;
+    int lo = 0, hi = SEG_SEL(SG, sg, n, s2);
     while (lo < hi) {                          // rows of s2 that come before (key, s, r): <= 12 steps
       const int mid = (lo + hi) >> 1;
       const unsigned k2 = rpn_key(other[(long)mid * 5]);
@@ -307,10 +322,13 @@ __global__ __launch_bounds__(256) void rpn_merge_kernel(const float* cand, RpnSe
   }
   if (rank >= maxp) return;
   float* d = dets + ((long)b * maxp + rank) * 5;
-  float* ro = rois + ((long)b * maxp + rank) * 5;
   d[0] = me[0]; d[1] = me[1]; d[2] = me[2]; d[3] = me[3];
   d[4] = sigmoid ? 1.f / (1.f + expf(-me[4])) : me[4];
-  ro[0] = (float)b; ro[1] = me[0]; ro[2] = me[1]; ro[3] = me[2]; ro[4] = me[3];
+  if (rois != nullptr) {
+    float* ro = rois + ((long)b * maxp + rank) * 5;
+    ro[0] = (float)b; ro[1] = me[0]; ro[2] = me[1]; ro[3] = me[2]; ro[4] = me[3];
+  }
+  if (labels != nullptr) labels[(long)b * maxp + rank] = s;
 }
 
 // the segment table of one image -> false: a length outside [0, HRF_RPN_MAX_PRE] or a count outside [1, HRF_RPN_MAX_LEVELS]
@@ -330,7 +348,8 @@ bool rpn_segs(const int* seg_len, int nseg, RpnSegs& sg) {
 inline long rpn_align(long v) { return (v + 255) / 256 * 256; }
 
 // bytes of the NMS part of a workspace: matrices, keep words, prefix counts
-long rpn_nms_bytes(const RpnSegs& sg, int B) {
+template <class SG>
+long rpn_nms_bytes(const SG& sg, int B) {
   return rpn_align((long)B * sg.mtot * 8) + rpn_align((long)B * sg.nseg * RPN_WORDS * 8) + rpn_align((long)B * sg.nseg * RPN_PREF * 4);
 }
 
@@ -357,21 +376,22 @@ bool rpn_check(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, RpnSegs& sg
   return rpn_segs(len, lv->num_levels, sg);
 }
 
-int rpn_launch_nms(const float* cand, const int* valid, const RpnSegs& sg, int B, int maxp, float thr, int sigmoid, char* ws,
-                   float* dets, int* count, float* rois, void* stream) {
+template <class SG>
+int rpn_launch_nms(const float* cand, const int* valid, const SG& sg, int B, int maxp, float thr, int sigmoid, char* ws,
+                   float* dets, int* count, float* rois, int* labels, void* stream) {
   rpn_u64* mask = reinterpret_cast<rpn_u64*>(ws);
   rpn_u64* keepw = reinterpret_cast<rpn_u64*>(ws + rpn_align((long)B * sg.mtot * 8));
   int* pref = reinterpret_cast<int*>(reinterpret_cast<char*>(keepw) + rpn_align((long)B * sg.nseg * RPN_WORDS * 8));
   int nbmax = 0;
   for (int s = 0; s < sg.nseg; ++s) nbmax = max(nbmax, (sg.n[s] + 63) / 64);
   if (nbmax > 0) {
-    HRF_LAUNCH(rpn_nms_tile_kernel, dim3(nbmax, nbmax, B * sg.nseg), dim3(64), 0, stream, cand, sg, thr, mask);
+    HRF_LAUNCH((rpn_nms_tile_kernel<SG>), dim3(nbmax, nbmax, B * sg.nseg), dim3(64), 0, stream, cand, sg, thr, mask);
     if (hrf_check_launch() != HRF_OK) return HRF_ERR_LAUNCH;
   }
-  HRF_LAUNCH(rpn_nms_reduce_kernel, dim3(B * sg.nseg), dim3(64), 0, stream, valid, sg, (const rpn_u64*)mask, keepw, pref);
+  HRF_LAUNCH((rpn_nms_reduce_kernel<SG>), dim3(B * sg.nseg), dim3(64), 0, stream, valid, sg, (const rpn_u64*)mask, keepw, pref);
   if (hrf_check_launch() != HRF_OK) return HRF_ERR_LAUNCH;
-  HRF_LAUNCH(rpn_merge_kernel, dim3(hrf_cdiv(max(sg.ktot, maxp), 256), B), dim3(256), 0, stream, cand, sg, (const rpn_u64*)keepw,
-             (const int*)pref, maxp, sigmoid, dets, count, rois);
+  HRF_LAUNCH((rpn_merge_kernel<SG>), dim3(hrf_cdiv(max(sg.ktot, maxp), 256), B), dim3(256), 0, stream, cand, sg, (const rpn_u64*)keepw,
+             (const int*)pref, maxp, sigmoid, dets, count, rois, labels);
   return hrf_check_launch();
 }
 
@@ -410,7 +430,7 @@ extern "C" int hrf_nms_segments(const float* cand, const int* valid, const int* 
   if (max_per_img < 1 || !(iou_thr > 0.f && iou_thr <= 1.f)) return HRF_ERR_ARG;
   if (workspace == nullptr || workspace_bytes < rpn_nms_bytes(sg, B) || dets == nullptr || count == nullptr || rois == nullptr) return HRF_ERR_ARG;
   if (sg.ktot > 0 && cand == nullptr) return HRF_ERR_ARG;
-  return rpn_launch_nms(cand, valid, sg, B, max_per_img, iou_thr, apply_sigmoid ? 1 : 0, static_cast<char*>(workspace), dets, count, rois, stream);
+  return rpn_launch_nms(cand, valid, sg, B, max_per_img, iou_thr, apply_sigmoid ? 1 : 0, static_cast<char*>(workspace), dets, count, rois, nullptr, stream);
 }
 
 extern "C" int hrf_rpn_proposals(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, const float* img_shape, void* workspace,
@@ -425,5 +445,5 @@ extern "C" int hrf_rpn_proposals(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t
   HRF_LAUNCH(rpn_select_decode_kernel, dim3(lv->num_levels, lv->B), dim3(RPN_NT), 0, stream, *lv, sg, cfg->min_bbox_size, img_shape, cand,
              valid, (int*)nullptr);
   if (hrf_check_launch() != HRF_OK) return HRF_ERR_LAUNCH;
-  return rpn_launch_nms(cand, valid, sg, lv->B, cfg->max_per_img, cfg->iou_thr, 1, nms, dets, count, rois, stream);
+  return rpn_launch_nms(cand, valid, sg, lv->B, cfg->max_per_img, cfg->iou_thr, 1, nms, dets, count, rois, nullptr, stream);
 }

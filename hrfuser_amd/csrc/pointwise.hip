@@ -2109,3 +2109,6 @@ extern "C" int hrf_memset(void* ptr, int value, long bytes, void* stream) {
 
 // RPN proposal generation (top-k + decode, per-level NMS, merge): hrf_rpn_select_decode / hrf_nms_segments / hrf_rpn_proposals
 #include "hrf_rpn.h"
+
+// cascade bbox head at test time (box refinement, softmax + per-class NMS + top-k): hrf_bbox_refine / hrf_bbox_detect
+#include "hrf_bbox.h"

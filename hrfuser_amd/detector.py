@@ -26,9 +26,11 @@ def combine_mod_imgs(lidar_img=None, radar_img=None, gated_img=None):
 class FeatureExtractor(nn.Module):
     """backbone (+ neck) of a `TwoStageDetector` config: `FeatureExtractor(cfg.model.backbone, cfg.model.neck)`;
     `bbox_roi_extractor` (optional): the `roi_head.bbox_roi_extractor` dict of the config (hrfuser_amd.roi); `rpn_head`
-    (optional): the `rpn_head` dict of the config plus `test_cfg=cfg.model.test_cfg.rpn` (hrfuser_amd.rpn)."""
+    (optional): the `rpn_head` dict of the config plus `test_cfg=cfg.model.test_cfg.rpn` (hrfuser_amd.rpn); `roi_head`
+    (optional): the `roi_head` dict of the config plus `test_cfg=cfg.model.test_cfg.rcnn` (hrfuser_amd.roi_head) - with it and
+    an rpn_head, `detect` / `simple_test` go from the images to detections."""
 
-    def __init__(self, backbone, neck=None, bbox_roi_extractor=None, rpn_head=None):
+    def __init__(self, backbone, neck=None, bbox_roi_extractor=None, rpn_head=None, roi_head=None):
         super().__init__()
         self.backbone = BACKBONES.build(backbone) if isinstance(backbone, dict) else backbone      # two_stage.py:41
         if neck is not None:
@@ -38,6 +40,8 @@ class FeatureExtractor(nn.Module):
                                        else bbox_roi_extractor)
         if rpn_head is not None:                                                                    # two_stage.py:46-50
             self.rpn_head = HEADS.build(rpn_head) if isinstance(rpn_head, dict) else rpn_head
+        if roi_head is not None:                                                                    # two_stage.py:52-58
+            self.roi_head = HEADS.build(roi_head) if isinstance(roi_head, dict) else roi_head
 
     @property
     def with_neck(self):
@@ -88,6 +92,30 @@ class FeatureExtractor(nn.Module):
         if rois is None:
             rois = self._proposals(x, img, img_shapes, None)[2]
         return self.bbox_roi_extractor(x, rois)
+
+    def detect(self, img, img_shapes=None, scale_factors=None, lidar_img=None, radar_img=None, gated_img=None):
+        """The whole test-time forward with fixed shapes (two_stage.py:178-186 `rpn_head.simple_test_rpn` + `roi_head.simple_test`):
+        extract_feat -> RPNHead.proposals -> CascadeRoIHead.detect -> (dets (B,max_per_img,5), labels (B,max_per_img) int32,
+        count (B,) int32).  No synchronisation.  img_shapes: (B,2) device tensor or list of (h, w[, c]), None: the padded input
+        size; scale_factors: (B,4) device tensor or list (boxes are divided by it), None: no rescale."""
+        if getattr(self, 'roi_head', None) is None:
+            raise ValueError('FeatureExtractor.detect: built without a roi_head')
+        from .rpn import _shapes
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        if img_shapes is None:
+            img_shapes = [tuple(img.shape[-2:])] * img.shape[0]
+        shp = _shapes(img_shapes, img.shape[0], x[0].device)
+        _, count, rois = self._proposals(x, img, shp, None)
+        return self.roi_head.detect(x, rois, count, shp, scale_factors)
+
+    def simple_test(self, img, img_metas, rescale=False, lidar_img=None, radar_img=None, gated_img=None):
+        """two_stage.py:205-226 without precomputed proposals: per image a list of num_classes (n, 5) numpy arrays.  The
+        modalities come wrapped in one-entry lists, as test pipelines deliver them.  SYNCHRONISES."""
+        if getattr(self, 'roi_head', None) is None or getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor.simple_test: built without an rpn_head / roi_head')
+        x = self.simple_test_feats(img, lidar_img, radar_img, gated_img)
+        proposal_list = self.rpn_head.simple_test_rpn(x, img_metas)
+        return self.roi_head.simple_test(x, proposal_list, img_metas, rescale=rescale)
 
     def forward(self, img, lidar_img=None, radar_img=None, gated_img=None):
         """The feature part of forward_train (two_stage.py:156-160): sensors by keyword."""

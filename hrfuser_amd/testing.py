@@ -235,3 +235,90 @@ def rpn_proposals_ref(cls_scores, bbox_preds, img_shapes, strides, bases, nms_pr
     """RPNHead.get_bboxes -> [(n_b, 5)] per image: (x1, y1, x2, y2, score)"""
     st1 = rpn_stage1_ref(cls_scores, bbox_preds, img_shapes, strides, bases, nms_pre, min_bbox_size)
     return [nms_segments_ref(levels, iou_thr, max_per_img)[0] for levels in st1]
+
+
+# ----------------------------------------------------------------------------- CascadeRoIHead.simple_test restatement
+# The oracle of hrfuser_amd.roi_head / csrc/hrf_bbox.h / csrc/hrf_fc.h: a literal torch restatement of cascade_roi_head.py:288-400,
+# bbox_head.py:316-378 / :460-497, convfc_bbox_head.py (Shared2FCBBoxHead.forward), bbox_nms.py:8-95 and delta_xywh_bbox_coder.py:
+# 224-260 with mmcv 1.3.17 nms (offset 0) per class.  Where the reference leaves the result open the header's rule is taken: equal
+# scores go to the lower class, then the lower roi row; a NaN score is invalid; classes are separate NMS problems.
+def bbox_delta2bbox(rois, deltas, stds=(1., 1., 1., 1.), max_shape=None, wh_ratio_clip=16 / 1000):
+    """delta2bbox (delta_xywh_bbox_coder.py:224-260) with means 0: `deltas * stds` first, then rpn_delta2bbox's order"""
+    return rpn_delta2bbox(rois, deltas * deltas.new_tensor(stds).view(1, -1), max_shape=max_shape, wh_ratio_clip=wh_ratio_clip)
+
+
+def bbox_head_ref(x, sd, prefix=''):
+    """Shared2FCBBoxHead.forward (convfc_bbox_head.py:155-191) in the dtype of `x` (K,C,7,7) with mmdet's state-dict keys ->
+    (cls_score (K, num_classes + 1), bbox_pred (K, 4))"""
+    import torch.nn.functional as F
+    p = lambda k: sd[prefix + k].to(x.dtype)                            # noqa: E731
+    h = x.flatten(1)
+    for i in (0, 1):
+        h = F.relu(F.linear(h, p(f'shared_fcs.{i}.weight'), p(f'shared_fcs.{i}.bias')))
+    return F.linear(h, p('fc_cls.weight'), p('fc_cls.bias')), F.linear(h, p('fc_reg.weight'), p('fc_reg.bias'))
+
+
+def multiclass_nms_ref(boxes, scores, score_thr, iou_thr, max_per_img, row_valid=None):
+    """multiclass_nms (bbox_nms.py:8-95) of ONE image with class-agnostic boxes (n,4) and scores (n, num_classes + 1) fp32 ->
+    (dets (m,5), labels (m,) int64, src (m,) int64 = the roi row of every output row).  Per class: candidates in descending score
+    order (stable: lower row first), valid = score > score_thr (NaN fails) and row_valid, greedy NMS on nms_greedy_ref; the kept
+    rows of all classes in a stable descending sort by score (ties: lower class, then lower row), [:max_per_img]"""
+    n, C = scores.shape[0], scores.shape[1] - 1
+    rows, labels, src = [], [], []
+    for c in range(C):
+        s = scores[:, c]
+        nan = torch.isnan(s)
+        order = torch.argsort(torch.where(nan, torch.full_like(s, float('-inf')), s), descending=True, stable=True)
+        order = torch.cat([order[~nan[order]], order[nan[order]]])
+        valid = s[order] > score_thr
+        if row_valid is not None:
+            valid = valid & row_valid[order]
+        keep = nms_greedy_ref(boxes[order], valid, iou_thr)
+        sel = order[keep]
+        rows.append(torch.cat([boxes[sel], s[sel, None]], dim=1))
+        labels.append(torch.full_like(sel, c))
+        src.append(sel)
+    rows, labels, src = torch.cat(rows), torch.cat(labels), torch.cat(src)
+    order = torch.argsort(rows[:, 4], descending=True, stable=True)[:max_per_img]
+    return rows[order], labels[order], src[order]
+
+
+def bbox_detect_ref(rois, logits, deltas, stds, img_shapes, counts, score_thr, iou_thr, max_per_img, scale_factors=None):
+    """the last stage's get_bboxes (bbox_head.py:316-378) on fixed-shape inputs: rois (B*R,5), logits = [(B*R, C+1)] per stage,
+    deltas (B*R,4), counts [n_b] (rows >= n_b of image b are invalid) -> [(dets, labels, src)] per image"""
+    B = len(img_shapes)
+    R = rois.shape[0] // B
+    mean = sum(logits) / float(len(logits))
+    out = []
+    for b in range(B):
+        sl = slice(b * R, (b + 1) * R)
+        scores = torch.softmax(mean[sl], dim=-1)
+        boxes = bbox_delta2bbox(rois[sl, 1:], deltas[sl], stds, max_shape=img_shapes[b])
+        if scale_factors is not None:
+            boxes = boxes / boxes.new_tensor(scale_factors[b])
+        out.append(multiclass_nms_ref(boxes, scores, score_thr, iou_thr, max_per_img, torch.arange(R) < int(counts[b])))
+    return out
+
+
+def cascade_simple_test_ref(feats, rois, counts, img_shapes, sds, stds_per_stage, strides, score_thr, iou_thr, max_per_img,
+                            scale_factors=None, finest_scale=56, dtype=torch.float32):
+    """CascadeRoIHead.simple_test (cascade_roi_head.py:288-400) on fixed-shape rois (B*R,5) with counts [n_b]: per stage
+    roi_extract_ref -> bbox_head_ref -> regress_by_class (class-agnostic), then bbox_detect_ref on the stage-averaged logits.
+    feats: NCHW maps; sds: one mmdet state dict per stage.  RoI features and the head run in `dtype`, the box arithmetic in fp32.
+    -> ([(dets, labels, src)] per image, per-stage list of the rois that entered the stage)"""
+    B = len(img_shapes)
+    R = rois.shape[0] // B
+    rois = rois.float().clone()
+    logits, stage_rois, deltas = [], [], None
+    for i, sd in enumerate(sds):
+        stage_rois.append(rois.clone())
+        x = roi_extract_ref([f.to(dtype) for f in feats], rois.to(dtype), strides, finest_scale)
+        cls, deltas = bbox_head_ref(x, sd)
+        cls, deltas = cls.float(), deltas.float()
+        logits.append(cls)
+        if i < len(sds) - 1:
+            new = [torch.cat([rois[b * R:(b + 1) * R, :1],
+                              bbox_delta2bbox(rois[b * R:(b + 1) * R, 1:], deltas[b * R:(b + 1) * R], stds_per_stage[i], max_shape=img_shapes[b])], dim=1)
+                   for b in range(B)]
+            rois = torch.cat(new)
+    return bbox_detect_ref(rois, logits, deltas, stds_per_stage[-1], img_shapes, counts, score_thr, iou_thr, max_per_img, scale_factors), stage_rois

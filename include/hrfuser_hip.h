@@ -491,6 +491,70 @@ int hrf_nms_segments(const float* cand, const int* valid, const int* seg_len, in
                      int apply_sigmoid, void* workspace, long workspace_bytes, float* dets, int* count, float* rois, void* stream);
 int hrf_rpn_proposals(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, const float* img_shape, void* workspace,
                       long workspace_bytes, float* dets, int* count, float* rois, void* stream);
+
+/* ---- Cascade bbox head at test time (csrc/hrf_fc.h in csrc/conv3w_engine.hip; csrc/hrf_bbox.h in csrc/pointwise.hip) ----------
+ * What CascadeRoIHead.simple_test does after RoIAlign (mmdet/models/roi_heads/cascade_roi_head.py:288-400, bbox_heads/
+ * bbox_head.py:316-378 / :460-497, convfc_bbox_head.py, core/post_processing/bbox_nms.py:8-95, delta_xywh_bbox_coder.py:224-260):
+ * the fully connected layers, the box refinement between stages and the final softmax / per-class NMS / top-k.  fp32, test time
+ * only.  Every entry validates its arguments (HRF_ERR_ARG before any launch), reads no device data on the host, allocates
+ * nothing, never synchronises, uses no float atomics (the same bits in deterministic mode and from run to run), bounds every
+ * loop by a size known at launch and can be captured in a hipGraph.
+ *
+ * hrf_fc  y[m][n] = act(bias[n] + sum_k x[m][k] * wp[n][k]), act = ReLU when relu == 1 (a NaN stays a NaN): a few rows, a deep K.
+ *   x [M] rows of pitch ldX >= K (the pad columns are never read), wp [N][K] from hrf_fc_pack (= hrf_rowgemm_pack, dir 0), bias [N]
+ *   or null, y [M] rows of pitch ldY >= N.  K % 16 == 0, N % 16 == 0, N <= 65536, 0 <= M <= 2^24; M == 0: HRF_OK, no launch.
+ *   fp32 MFMA with hrf_rowgemm's operand precision and tile; the K steps are split over blocks (a function of (M, K, N) alone) so
+ *   that M ~ 2000, K = 12544, N = 1024 is 512 blocks, the partial sums go through slots of `workspace`
+ *   (hrf_fc_workspace_bytes(M, K, N) bytes, 0 when the shape is not split or refused; caller-owned, contents irrelevant, 16-byte
+ *   aligned) and are folded in slot order by a second launch that also applies bias / ReLU.  No atomics, no arrival counters.
+ *   REFUSED: K % 16 != 0, N % 16 != 0, K / N < 1, M < 0, a null x / wp / y, ldX < K, ldY < N, relu not 0 / 1, a workspace that
+ *   is null or too small when one is needed.
+ * hrf_bbox_refine  regress_by_class with reg_class_agnostic: rois_out[r] = (rois_in[r][0], delta2bbox(rois_in[r][1:5],
+ *   deltas[r][0:4] * stds, clipped to img_shape[b])), b = rois_in[r][0], in the written fp32 order: deltas * stds first, dw / dh
+ *   clamped to +-|log(16 / 1000)|, one expf per side, the clip to [0, w] / [0, h].  deltas: rows of pitch ld_deltas >= 4 (a
+ *   column slice of the padded head output); img_shape: the device [B][2] (h, w) array of the RPN entries.  A row whose batch
+ *   index is not an integer in [0, B) (also NaN) keeps its first column and gets the box (0, 0, 0, 0) - hrf_roi_align_fwd gives
+ *   such a row zeros - and img_shape is never indexed with it.  A padded row (b, 0, 0, 0, 0) stays (b, 0, 0, 0, 0) for finite
+ *   deltas.  rois_out may be rois_in.  REFUSED: a null pointer, ld_deltas < 4, B < 1, K < 0, a std that is not positive and finite.
+ * hrf_bbox_detect  the last stage's get_bboxes: for row r of image b (rows b * R ..) score = softmax((sum_s logits_s) / S) over
+ *   the num_classes + 1 columns (background last; the sum in stage order), box = delta2bbox(rois[r][1:5], deltas[r] * stds)
+ *   clipped to img_shape[b] and then, when scale_factor ([B][4], nullable: no rescale) is given, divided by it.  Candidate (r, c),
+ *   c < num_classes, is valid iff score > score_thr (a NaN score fails) and r < count[b] (count nullable: all R rows).  Each
+ *   (image, class) is put in descending score order (equal scores: lower row) and goes through the greedy NMS of
+ *   hrf_nms_segments (same IoU formula and fp32 order; classes are independent, mmcv's coordinate offsets are not reproduced);
+ *   the kept rows of an image are merged by score descending - ties: lower class, then lower row - and the first max_per_img are
+ *     dets   [B][max_per_img][5] (x1, y1, x2, y2, score), rows past count_out[b] zero;
+ *     labels [B][max_per_img] int32, -1 past count_out[b];   count_out [B] int32.
+ *   logits / deltas: rows of pitch ld_logits >= num_classes + 1 / ld_deltas >= 4.  workspace: hrf_bbox_detect_workspace_bytes(B, R,
+ *   num_classes) bytes (0 for what is refused), 256-byte aligned, caller-owned, contents irrelevant.  REFUSED: R outside
+ *   [1, HRF_RPN_MAX_PRE], num_classes outside [1, HRF_BBOX_MAX_CLASSES], num_stages outside [1, HRF_BBOX_MAX_STAGES], B < 1 or
+ *   B * HRF_BBOX_MAX_CLASSES > 65535, a pitch smaller than the row, a null pointer (count / scale_factor excepted), a std that is
+ *   not positive and finite, max_per_img < 1, score_thr outside [0, 1], iou_thr outside (0, 1], a workspace that is too small. */
+#define HRF_BBOX_MAX_CLASSES 16
+#define HRF_BBOX_MAX_STAGES 4
+typedef struct hrf_bbox_det {
+  int B, R, num_classes, num_stages;
+  const float* rois;                     /* [B * R][5] (b, x1, y1, x2, y2): the last stage's input rois */
+  const int* count;                      /* [B] valid rows per image, nullable */
+  const float* logits[HRF_BBOX_MAX_STAGES];
+  int ld_logits;
+  const float* deltas;                   /* the last stage's */
+  int ld_deltas;
+  float stds[4];
+  const float* img_shape;                /* [B][2] (h, w) */
+  const float* scale_factor;             /* [B][4], nullable */
+  float score_thr, iou_thr;
+  int max_per_img;
+} hrf_bbox_det_t;
+long hrf_fc_workspace_bytes(long M, int K, int N);
+int hrf_fc_pack(const float* w, int N, int K, int Np, int Kp, float* wp, void* stream);
+int hrf_fc(const float* x, int ldX, const float* wp, const float* bias, float* y, int ldY, int relu, long M, int K, int N,
+           void* workspace, long workspace_bytes, void* stream);
+int hrf_bbox_refine(const float* rois_in, const float* deltas, int ld_deltas, float std_x, float std_y, float std_w, float std_h,
+                    const float* img_shape, int B, long K, float* rois_out, void* stream);
+long hrf_bbox_detect_workspace_bytes(int B, int R, int num_classes);
+int hrf_bbox_detect(const hrf_bbox_det_t* d, void* workspace, long workspace_bytes, float* dets, int* labels, int* count_out,
+                    void* stream);
 /* the same gather for EVERY fused layer of a step in one launch: seg = nseg rows of 5 longs on the device {offset (floats) of the
  * layer's ds_plane in `planes`, windows, heads, address of its drpb accumulator, copy_stride}; max_nwin / max_heads = the
  * largest of the rows (launch geometry).                                                                               */
