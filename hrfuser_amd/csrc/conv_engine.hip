@@ -1169,7 +1169,9 @@ extern "C" __attribute__((visibility("hidden"))) int hrf_lin2_knob(int key, int 
 extern "C" __attribute__((visibility("hidden"))) int hrf_w3x_knob(int key, int value);
 extern "C" __attribute__((visibility("hidden"))) int hrf_dw_knob(int key, int value);
 extern "C" __attribute__((visibility("hidden"))) int hrf_ab_knob(int key, int value);
+extern "C" __attribute__((visibility("hidden"))) int hrf_rpnt_knob(int key, int value);
 extern "C" int hrf_debug_knob(int key, int value) {
+  if (key >= 44 && key < 48) return hrf_rpnt_knob(key - 44, value);    // hrf_rpn_train.h: 44 = return after the first `value` launches of hrf_rpn_assign / hrf_rpn_loss (0: all)
   if (key >= 36 && key < 40) return hrf_ab_knob(key - 36, value);      // attn_block.hip: 36 = wave-group form of the forward (0 auto, 1 / 2 / 4), 37 = query the form of width `value`
   if (key >= 40 && key < 44) return hrf_dw_knob(key - 40, value);      // dwconv.hip: 40 = float4-lane kernels (1 off, 2 / 3 tile height), 41 = grid threshold
   if (key >= 32 && key < 36) return hrf_w3x_knob(key - 32, value);     // wgrad3x_engine.hip: 32 = blocks per problem, 33 = smallest problem (output pixels)

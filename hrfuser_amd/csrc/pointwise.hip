@@ -2112,3 +2112,6 @@ extern "C" int hrf_memset(void* ptr, int value, long bytes, void* stream) {
 
 // cascade bbox head at test time (box refinement, softmax + per-class NMS + top-k): hrf_bbox_refine / hrf_bbox_detect
 #include "hrf_bbox.h"
+
+// RPN training targets and loss (inside flags, MaxIoUAssigner, sampler, BCE + SmoothL1 and their gradients): hrf_rpn_assign / hrf_rpn_loss
+#include "hrf_rpn_train.h"

@@ -82,6 +82,18 @@ class FeatureExtractor(nn.Module):
         x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
         return self._proposals(x, img, img_shapes, cfg)
 
+    def rpn_loss(self, img, gt_bboxes, img_metas=None, lidar_img=None, radar_img=None, gated_img=None):
+        """extract_feat -> rpn_head -> loss (two_stage.py:163-172 `rpn_head.forward_train` without the proposals): mmdet's dict of
+        per-level lists.  gt_bboxes / img_metas as RPNHead.loss takes them; img_metas None: every image has the padded input size.
+        The head's forward is eval only, so the losses carry no gradient into the pyramid: the gradient maps on the head's outputs
+        are what RPNHead.loss keeps."""
+        if getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor.rpn_loss: built without an rpn_head')
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        if img_metas is None:
+            img_metas = [dict(img_shape=tuple(img.shape[-2:]), pad_shape=tuple(img.shape[-2:]))] * img.shape[0]
+        return self.rpn_head.loss(*self.rpn_head(x), gt_bboxes, img_metas)
+
     def extract_roi_feats(self, img, rois=None, lidar_img=None, radar_img=None, gated_img=None, img_shapes=None):
         """extract_feat followed by the RoI extractor (standard_roi_head.py:116-118: `bbox_roi_extractor(x[:num_inputs],
         rois)`): rois (K,5) = (batch index, x1, y1, x2, y2) -> (K, out_channels, 7, 7).  rois None: the `rois` of the RPN head

@@ -136,6 +136,15 @@ def work_model(name, a):
         return ('rpn_select_decode_kernel' if name.endswith('decode') else 'rpn_proposals (4 kernels)'), 0.0, f4 * 5.0 * n
     if name == 'hrf_nms_segments':
         return 'rpn_nms (3 kernels)', 0.0, 0.0
+    if name in ('hrf_rpn_assign', 'hrf_rpn_loss'):
+        # RPN training targets / loss (csrc/hrf_rpn_train.h: rpnt_iou_kernel, rpnt_gtmax_kernel, rpnt_assign_kernel, rpnt_select_kernel,
+        # rpnt_loss_kernel<false / true>, rpnt_finalize_kernel), priced by the per-anchor traffic: max_iou, argmax, assigned and sampled
+        # written, argmax / assigned read back by launches 2 - 5 (the select reads `assigned` once per radix pass, about five times);
+        # the loss adds the logit and five gradient floats per anchor.  The IoU arithmetic (two evaluations per anchor and gt of
+        # about 12 flops) is the flop count - tools/rpn_loss_cost.py times the launches one by one
+        n = float(a['B']) * a['anchors']
+        loss = name.endswith('loss')
+        return ('rpn_loss (6 kernels)' if loss else 'rpn_assign (5 kernels)'), 0.0, f4 * n * (12.0 + (6.0 if loss else 0.0))
     if name == 'hrf_conv3_packed_bf16x3':
         # bf16x3 matrix mode of the wide 3x3 engine: the algorithmic work of the convolution (one multiply-add per term, whatever
         # the three split products cost - MFMA_ROOF prices those) and its fp32 rows and pack
@@ -223,7 +232,7 @@ class ProfLib:
                 d['B'], d['H'], d['W'], d['A'] = lv.B, lv.H[0], lv.W[0], lv.A
                 d['anchors'] = sum(lv.H[l] * lv.W[l] for l in range(lv.num_levels)) * lv.A
                 cfg = d.get('cfg')
-                d['nms_pre'] = cfg.nms_pre if isinstance(cfg, ctypes.Structure) else 0
+                d['nms_pre'] = getattr(cfg, 'nms_pre', 0) if isinstance(cfg, ctypes.Structure) else 0     # (hrf_rpn_train_cfg_t has none)
             elif isinstance(lv, ctypes.Structure):        # hrf_roi_levels_t: channels, batch and the finest map
                 d['C'], d['B'], d['H'], d['W'], d['HW0'] = lv.C, lv.B, lv.H[0], lv.W[0], lv.H[0] * lv.W[0]
             return d

@@ -2,7 +2,8 @@
 (configs/_base_/models/cascade_rcnn_hrfuser_fpn_*_fusion.py:132-147; two_stage.py: extract_feat -> rpn_head -> roi_head).
 
 Drop-in for mmdet's `RPNHead` (mmdet/models/dense_heads/rpn_head.py) at test time: same registry name, constructor keywords
-and state-dict keys (`rpn_conv.*`, `rpn_cls.*`, `rpn_reg.*`).  Eval / forward only: there is no tape, `loss` raises.
+and state-dict keys (`rpn_conv.*`, `rpn_cls.*`, `rpn_reg.*`).  The forward is eval only (no tape for the head's own three
+convolutions); with a `train_cfg` the head computes mmdet's RPN losses and their gradients on its output maps.
 
   forward      3x3 conv 256 -> 256 on the wide packed engine (hrf_conv3_pack + hrf_conv3_packed, the launches of
                neck._conv3_wide), one ReLU launch (hrf_affine_act_res), and BOTH 1x1 convolutions as ONE padded row GEMM
@@ -11,9 +12,12 @@ and state-dict keys (`rpn_conv.*`, `rpn_cls.*`, `rpn_reg.*`).  Eval / forward on
   proposals    csrc/hrf_rpn.h in four launches: per-level top-k + decode, per-level NMS (bit matrix + one wave per level),
                merge.  Fixed-shape outputs (dets, count, rois), no host read, no synchronisation: capturable in a hipGraph.
   get_bboxes   mmdet's return type - a list of (n_i, 5) - which slices by `count` and therefore SYNCHRONISES.
+  loss         csrc/hrf_rpn_train.h in six launches: IoU + argmax per anchor, the best IoU per gt, MaxIoUAssigner, the sampler's
+               radix select, BCE-with-logits + SmoothL1 with their gradient maps, the per-level sums.  Fixed shapes, no host
+               read: capturable.  The values reach torch.autograd through `_RpnLossFn`.
 
-Three functional entries underneath (`select_decode`, `nms_segments`, `rpn_proposals`) take NHWC maps / candidate rows
-directly.  There is no CPU fallback.
+Five functional entries underneath (`select_decode`, `nms_segments`, `rpn_proposals`, `rpn_assign`, `rpn_loss`) take NHWC maps /
+candidate rows directly.  There is no CPU fallback.
 """
 import ctypes
 
@@ -153,6 +157,118 @@ def rpn_proposals(cls_maps, reg_maps, img_shapes, strides, bases, nms_pre, max_p
     return dets, count, rois
 
 
+# ----------------------------------------------------------------------------- training targets and loss (csrc/hrf_rpn_train.h)
+MAX_GT = _lib._header_int('HRF_RPN_MAX_GT', 256)
+GRAD_PITCH = 16                                 # floats per position of a gradient buffer: cls in [:A], reg in [A:5A] - the dY of the head's row GEMM
+
+
+def train_cfg_struct(pos_iou_thr=0.7, neg_iou_thr=0.3, min_pos_iou=0.3, match_low_quality=True, allowed_border=0, num=256, num_pos=128,
+                     beta=1.0 / 9.0, loss_weight_cls=1.0, loss_weight_bbox=1.0):
+    """hrf_rpn_train_cfg_t; num_pos = int(num * pos_fraction)"""
+    c = _lib.RpnTrainCfg()
+    c.pos_iou_thr, c.neg_iou_thr, c.min_pos_iou = float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou)
+    c.match_low_quality, c.allowed_border, c.num, c.num_pos = int(bool(match_low_quality)), int(allowed_border), int(num), int(num_pos)
+    c.beta, c.loss_weight_cls, c.loss_weight_bbox = float(beta), float(loss_weight_cls), float(loss_weight_bbox)
+    return c
+
+
+def pack_gts(gt_bboxes, dev, gmax=None):
+    """list of (n_i, 4) boxes -> (gt (B,Gmax,4) fp32, gt_count (B,) int32) on `dev`.  The counts are the shapes: no device value
+    is read, nothing synchronises.  gmax: the fixed Gmax (a captured graph needs one), default max(n_i, 1)."""
+    ns = [int(t.shape[0]) for t in gt_bboxes]
+    gmax = max(ns + [1]) if gmax is None else int(gmax)
+    if max(ns + [0]) > gmax or not 1 <= gmax <= MAX_GT:
+        raise NotImplementedError(f'rpn on the HIP engine: {max(ns + [0])} ground-truth boxes in an image with Gmax {gmax} are not built (1..{MAX_GT})')
+    gt = torch.zeros((len(ns), gmax, 4), device=dev, dtype=torch.float32)
+    for b, t in enumerate(gt_bboxes):
+        if ns[b]:
+            gt[b, :ns[b]] = t.detach().reshape(-1, 4).to(device=dev, dtype=torch.float32)
+    return gt, torch.tensor(ns, dtype=torch.int32).to(dev)
+
+
+def rng_state(seed, counter=0, device='cpu'):
+    """the (seed, counter) pair the kernels draw sampling keys from: int32 (2,) holding two uint32 values"""
+    v = [int(x) & 0xffffffff for x in (seed, counter)]
+    return torch.tensor([x - (1 << 32) if x >= (1 << 31) else x for x in v], dtype=torch.int32).to(device)
+
+
+def _train_args(cls_maps, reg_maps, img_shapes, pad_shapes, gt, gt_count, strides, bases, cfg, keys, rng, workspace):
+    L = _check(cls_maps, reg_maps, strides, bases)
+    dev, B = cls_maps[0].device, cls_maps[0].shape[0]
+    N = sum(m.shape[1] * m.shape[2] * m.shape[3] for m in cls_maps)
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[2] != 4 or gt.dtype != torch.float32 or not gt.is_contiguous() or gt.device != dev:
+        raise ValueError(f'rpn: gt must be contiguous fp32 ({B}, Gmax, 4) on {dev}, got {tuple(gt.shape)} {gt.dtype} on {gt.device}')
+    if gt_count.shape != (B,) or gt_count.dtype != torch.int32 or gt_count.device != dev:
+        raise ValueError(f'rpn: gt_count must be int32 ({B},) on {dev}, got {tuple(gt_count.shape)} {gt_count.dtype} on {gt_count.device}')
+    if keys is not None and (keys.shape != (B, N) or keys.dtype != torch.int32 or not keys.is_contiguous() or keys.device != dev):
+        raise ValueError(f'rpn: keys must be contiguous int32 ({B}, {N}) holding uint32 values on {dev}, got {tuple(keys.shape)} {keys.dtype}')
+    if keys is None and (rng is None or rng.shape != (2,) or rng.dtype != torch.int32 or rng.device != dev):
+        raise ValueError(f'rpn: without keys an int32 (2,) rng_state (seed, counter) on {dev} is needed (rpn.rng_state)')
+    lv = _levels(cls_maps, reg_maps, strides, bases)
+    gmax = gt.shape[1]
+    if not L.hrf_rpn_train_supported(lv, cfg, gmax):
+        raise NotImplementedError(f'rpn targets on the HIP engine: Gmax {gmax} (1..{MAX_GT}), thresholds ({cfg.pos_iou_thr}, {cfg.neg_iou_thr}, '
+                                  f'{cfg.min_pos_iou}) in [0, 1], num {cfg.num} >= 1, num_pos {cfg.num_pos} in [0, num], beta {cfg.beta} > 0 or '
+                                  'the maps are not supported')
+    need = L.hrf_rpn_train_workspace_bytes(lv, cfg, gmax)
+    if workspace is None:
+        workspace = torch.empty((need,), device=dev, dtype=torch.uint8)
+    outs = (torch.empty((B, N), device=dev, dtype=torch.int32), torch.empty((B, N), device=dev, dtype=torch.float32),
+            torch.empty((B, N), device=dev, dtype=torch.int32), torch.empty((B, 4), device=dev, dtype=torch.int32))
+    return L, lv, _shapes(img_shapes, B, dev), _shapes(pad_shapes, B, dev), gmax, workspace, outs
+
+
+def rpn_assign(cls_maps, reg_maps, img_shapes, pad_shapes, gt, gt_count, strides, bases, cfg, keys=None, rng=None, workspace=None, stream=None):
+    """hrf_rpn_assign on NHWC views: inside flags, MaxIoUAssigner, sampler -> (assigned (B,N) int32, max_iou (B,N) fp32,
+    sampled (B,N) int32, counts (B,4) int32); N = the anchors of all levels, level after level.  cfg: train_cfg_struct(...);
+    gt / gt_count: pack_gts(...); keys (B,N) int32 (uint32 values) or rng = rng_state(seed, counter) (not advanced here)."""
+    L, lv, shp, pad, gmax, ws, outs = _train_args(cls_maps, reg_maps, img_shapes, pad_shapes, gt, gt_count, strides, bases, cfg, keys, rng, workspace)
+    L.hrf_rpn_assign(lv, cfg, shp, pad, gt, gt_count, gmax, keys, rng, ws, ws.numel(), *outs, _lib.stream_ptr() if stream is None else stream)
+    return outs
+
+
+def rpn_loss(cls_maps, reg_maps, img_shapes, pad_shapes, gt, gt_count, strides, bases, cfg, keys=None, rng=None, workspace=None, stream=None,
+             grads=None):
+    """hrf_rpn_loss on NHWC views -> (losses (2,L) fp32: loss_cls per level, loss_bbox per level; grads: per level ONE zero-padded
+    (B,H,W,16) buffer with d loss_cls_l / d cls in [..., :A] and d loss_bbox_l / d reg in [..., A:5A]; assigned, max_iou, sampled,
+    counts as rpn_assign).  With rng (no keys) the counter is advanced on the device by the call.  grads: buffers of an earlier
+    call to write into again (their padding columns are zero already) instead of new ones."""
+    L, lv, shp, pad, gmax, ws, outs = _train_args(cls_maps, reg_maps, img_shapes, pad_shapes, gt, gt_count, strides, bases, cfg, keys, rng, workspace)
+    dev, A = cls_maps[0].device, cls_maps[0].shape[3]
+    if grads is None:
+        grads = [torch.zeros(tuple(m.shape[:3]) + (GRAD_PITCH,), device=dev, dtype=torch.float32) for m in cls_maps]
+    if any(g.shape != tuple(m.shape[:3]) + (GRAD_PITCH,) or g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev
+           for g, m in zip(grads, cls_maps)) or len(grads) != len(cls_maps):
+        raise ValueError(f'rpn_loss: grads must be contiguous fp32 (B, H, W, {GRAD_PITCH}) buffers on {dev}, one per level')
+    gr = _lib.RpnGrads()
+    for l, g in enumerate(grads):
+        gr.d_cls[l], gr.d_reg[l] = g.data_ptr(), g.data_ptr() + 4 * A
+        gr.ld_cls[l] = gr.ld_reg[l] = GRAD_PITCH
+    losses = torch.empty((2, len(cls_maps)), device=dev, dtype=torch.float32)
+    L.hrf_rpn_loss(lv, cfg, shp, pad, gt, gt_count, gmax, keys, rng, ws, ws.numel(), *outs, gr, losses, _lib.stream_ptr() if stream is None else stream)
+    return (losses, grads) + outs
+
+
+class _RpnLossFn(torch.autograd.Function):
+    """torch.autograd bridge: any producer of cls_scores / bbox_preds trains against the HIP loss.  Forward runs hrf_rpn_loss and
+    keeps the gradient maps; backward scales them by the incoming per-loss gradients."""
+
+    @staticmethod
+    def forward(fctx, call, A, *maps):
+        n = len(maps) // 2
+        losses, grads = call([_rows(t, A, 'RPNHead.loss cls_scores') for t in maps[:n]], [_rows(t, 4 * A, 'RPNHead.loss bbox_preds') for t in maps[n:]])[:2]
+        fctx.hrf = (grads, A)
+        return losses
+
+    @staticmethod
+    def backward(fctx, gl):
+        grads, A = fctx.hrf
+        gl = gl.float()
+        dc = [(g[..., :A] * gl[0, l]).permute(0, 3, 1, 2) for l, g in enumerate(grads)]
+        dr = [(g[..., A:5 * A] * gl[1, l]).permute(0, 3, 1, 2) for l, g in enumerate(grads)]
+        return (None, None) + tuple(dc) + tuple(dr)
+
+
 def _not_built(key, value, why):
     return NotImplementedError(f'RPNHead on the HIP engine: {key}={value!r} is not built ({why})')
 
@@ -200,6 +316,8 @@ class RPNHead(nn.Module):
             raise _not_built('reg_decoded_bbox', reg_decoded_bbox, 'a training-only switch')
         if test_cfg is not None:
             self._proposal_cfg(test_cfg)                       # an unsupported nms type raises at build time
+        if train_cfg is not None:
+            self._train_cfg(train_cfg, loss_cls, loss_bbox)    # an unsupported assigner / sampler / loss raises at build time
         from .testing import rpn_base_anchors
         self.in_channels, self.feat_channels, self.num_convs = in_channels, feat_channels, num_convs
         self.anchor_generator, self.bbox_coder = dict(anchor_generator), dict(bbox_coder)
@@ -313,13 +431,127 @@ class RPNHead(nn.Module):
         """dense_test_mixins.py:116-131."""
         return self.get_bboxes(*self.forward(x), img_metas=img_metas)
 
+    @staticmethod
+    def _train_cfg(train_cfg, loss_cls, loss_bbox):
+        """-> the keywords of train_cfg_struct for a train_cfg.rpn dict + the two loss dicts; anything the kernels do not build raises"""
+        tc = dict(train_cfg)
+        asg, smp = dict(tc.pop('assigner', {})), dict(tc.pop('sampler', {}))
+        if asg.pop('type', None) != 'MaxIoUAssigner':
+            raise _not_built('train_cfg.assigner.type', train_cfg.get('assigner', {}).get('type'), 'MaxIoUAssigner in every HRFuser config')
+        pos, neg = asg.pop('pos_iou_thr', None), asg.pop('neg_iou_thr', None)
+        if not isinstance(neg, float) or not isinstance(pos, (int, float)):
+            raise _not_built('train_cfg.assigner.pos_iou_thr / neg_iou_thr', (pos, neg), 'two numbers; a (low, high) tuple for neg_iou_thr is not')
+        min_pos, mlq = float(asg.pop('min_pos_iou', 0.0)), bool(asg.pop('match_low_quality', True))
+        if asg.pop('ignore_iof_thr', -1) > 0:
+            raise _not_built('train_cfg.assigner.ignore_iof_thr', train_cfg['assigner']['ignore_iof_thr'], 'gt_bboxes_ignore is out of scope; -1 in every HRFuser config')
+        asg.pop('ignore_wrt_candidates', True)                      # (only read with ignore_iof_thr > 0)
+        if asg.pop('gt_max_assign_all', True) is not True:
+            raise _not_built('train_cfg.assigner.gt_max_assign_all', False, 'True, the default')
+        if asg.pop('gpu_assign_thr', -1) != -1:
+            raise _not_built('train_cfg.assigner.gpu_assign_thr', train_cfg['assigner']['gpu_assign_thr'], 'the assignment never leaves the device; -1')
+        if dict(asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))) != dict(type='BboxOverlaps2D') or asg:
+            raise _not_built('train_cfg.assigner keys', sorted(asg) or 'iou_calculator', 'unknown to the kernel')
+        if smp.pop('type', None) != 'RandomSampler':
+            raise _not_built('train_cfg.sampler.type', train_cfg.get('sampler', {}).get('type'), 'RandomSampler in every HRFuser config')
+        num, frac = smp.pop('num', None), smp.pop('pos_fraction', None)
+        if not isinstance(num, int) or num < 1 or frac is None or not 0.0 <= float(frac) <= 1.0:
+            raise _not_built('train_cfg.sampler.num / pos_fraction', (num, frac), 'num >= 1 and 0 <= pos_fraction <= 1')
+        if smp.pop('neg_pos_ub', -1) != -1:
+            raise _not_built('train_cfg.sampler.neg_pos_ub', train_cfg['sampler']['neg_pos_ub'], '-1 in every HRFuser config')
+        if smp.pop('add_gt_as_proposals', True) is not False:
+            raise _not_built('train_cfg.sampler.add_gt_as_proposals', train_cfg['sampler'].get('add_gt_as_proposals', True),
+                             'False for an RPN: ground truths are not anchors')
+        if smp:
+            raise _not_built('train_cfg.sampler keys', sorted(smp), 'unknown to the kernel')
+        if tc.get('pos_weight', -1) > 0:
+            raise _not_built('train_cfg.pos_weight', tc['pos_weight'], '-1 in every HRFuser config')
+        if tc.get('debug', False):
+            raise _not_built('train_cfg.debug', True, 'False')
+        lc, lb = dict(loss_cls or {}), dict(loss_bbox or {})
+        if lc.get('type') != 'CrossEntropyLoss' or not lc.get('use_sigmoid', False) or lc.get('use_mask', False) or lc.get('class_weight') is not None \
+                or lc.get('reduction', 'mean') != 'mean':
+            raise _not_built('loss_cls', loss_cls, 'a sigmoid CrossEntropyLoss with mean reduction')
+        if lb.get('type') != 'SmoothL1Loss' or lb.get('reduction', 'mean') != 'mean' or not float(lb.get('beta', 1.0)) > 0:
+            raise _not_built('loss_bbox', loss_bbox, 'a SmoothL1Loss with beta > 0 and mean reduction')
+        return dict(pos_iou_thr=float(pos), neg_iou_thr=neg, min_pos_iou=min_pos, match_low_quality=mlq, allowed_border=int(tc.get('allowed_border', 0)),
+                    num=num, num_pos=int(num * float(frac)), beta=float(lb.get('beta', 1.0)), loss_weight_cls=float(lc.get('loss_weight', 1.0)),
+                    loss_weight_bbox=float(lb.get('loss_weight', 1.0)))
+
+    def _no_train_cfg(self, what):
+        return NotImplementedError(f'RPNHead on the HIP engine: {what} is not built without train_cfg - the anchor assigner and sampler (train_cfg.'
+                                   'assigner / sampler) are named there; the head is forward / proposals only')
+
+    def rng(self, device):
+        """the device (seed, counter) pair the sampler draws from (rpn.rng_state); hrf_rpn_loss advances the counter"""
+        st = self.__dict__.get('_rng')
+        if st is None or st.device != torch.device(device):
+            st = self.__dict__['_rng'] = rng_state(int(torch.initial_seed()), 0, device)
+        return st
+
+    def _loss_call(self, cls_scores, gt_bboxes, img_metas, keys=None):
+        """-> f(cls_maps, reg_maps) = rpn_loss(...) with everything but the maps bound; gt_bboxes: a list of (n_i, 4) tensors or the
+        fixed-shape pair (gt (B,Gmax,4), gt_count (B,) int32) on the device"""
+        dev, n = cls_scores[0].device, len(cls_scores)
+        if isinstance(gt_bboxes, tuple) and len(gt_bboxes) == 2 and isinstance(gt_bboxes[0], torch.Tensor) and gt_bboxes[0].dim() == 3:
+            gt, gt_count = gt_bboxes
+        else:
+            gt, gt_count = pack_gts(gt_bboxes, dev)
+        cfg = train_cfg_struct(**self._train_cfg(self.train_cfg, self.loss_cls, self.loss_bbox))
+        shp = [m['img_shape'] for m in img_metas] if not isinstance(img_metas, tuple) else img_metas[0]
+        pad = [m.get('pad_shape', m['img_shape']) for m in img_metas] if not isinstance(img_metas, tuple) else img_metas[1]
+        bases, strides = [b.tolist() for b in self.base_anchors[:n]], self.strides[:n]
+        rng = None if keys is not None else self.rng(dev)
+        return lambda cm, rm: rpn_loss(cm, rm, shp, pad, gt, gt_count, strides, bases, cfg, keys=keys, rng=rng)
+
+    def get_targets(self, cls_scores, bbox_preds, gt_bboxes, img_metas, keys=None):
+        """The fixed-shape form of anchor_head.py:299-400: -> (assigned (B,N) int32: -2 not inside / -1 / 0 / i + 1, max_iou (B,N),
+        sampled (B,N) int32: +1 / -1 / 0, counts (B,4) int32) over the anchors of all levels, level after level.  Draws with the
+        head's current counter and does not advance it."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('get_targets')
+        A, dev = self.num_base_priors, cls_scores[0].device
+        cm = [_rows(t, A, 'RPNHead.get_targets cls_scores') for t in cls_scores]
+        rm = [_rows(t, 4 * A, 'RPNHead.get_targets bbox_preds') for t in bbox_preds]
+        gt, gt_count = gt_bboxes if isinstance(gt_bboxes, tuple) else pack_gts(gt_bboxes, dev)
+        n = len(cm)
+        return rpn_assign(cm, rm, [m['img_shape'] for m in img_metas], [m.get('pad_shape', m['img_shape']) for m in img_metas], gt, gt_count,
+                          self.strides[:n], [b.tolist() for b in self.base_anchors[:n]],
+                          train_cfg_struct(**self._train_cfg(self.train_cfg, self.loss_cls, self.loss_bbox)), keys=keys,
+                          rng=None if keys is not None else self.rng(dev))
+
     def loss(self, *args, **kwargs):
-        raise NotImplementedError('RPNHead on the HIP engine: loss is not built - the anchor assigner and sampler (train_cfg.assigner / '
-                                  'sampler) are out of scope; the head is forward / proposals only')
+        """rpn_head.py:70-101 -> dict(loss_rpn_cls=[per level], loss_rpn_bbox=[per level]).  Signature (cls_scores, bbox_preds,
+        gt_bboxes, img_metas, gt_bboxes_ignore=None); gt_bboxes: a list of (n_i, 4) tensors (packed without a synchronisation) or the
+        fixed-shape pair (gt (B,Gmax,4) fp32, gt_count (B,) int32) for a captured graph; img_metas: dicts with img_shape / pad_shape,
+        or the pair of (B,2) device tensors (img_shape, pad_shape).  The values carry a grad_fn: backward delivers the kernel's
+        gradient maps, scaled by the incoming gradients, to cls_scores / bbox_preds."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('loss')
+        return self._loss(*args, **kwargs)
+
+    def _loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None, keys=None):
+        if gt_bboxes_ignore is not None:
+            raise _not_built('gt_bboxes_ignore', 'given', 'ignore regions are out of scope')
+        if len(cls_scores) != len(bbox_preds) or len(cls_scores) > len(self.strides):
+            raise ValueError(f'RPNHead.loss: {len(cls_scores)} / {len(bbox_preds)} maps, {len(self.strides)} anchor strides')
+        call = self._loss_call(cls_scores, gt_bboxes, img_metas, keys)
+        losses = _RpnLossFn.apply(call, self.num_base_priors, *cls_scores, *bbox_preds)
+        n = len(cls_scores)
+        return dict(loss_rpn_cls=[losses[0, l] for l in range(n)], loss_rpn_bbox=[losses[1, l] for l in range(n)])
 
     def forward_train(self, *args, **kwargs):
-        raise NotImplementedError('RPNHead on the HIP engine: forward_train is not built - the anchor assigner and sampler (train_cfg.'
-                                  'assigner / sampler) are out of scope; the head is forward / proposals only')
+        """base_dense_head.py:303-346 -> losses, or (losses, proposal_list) with a proposal_cfg.  Signature (x, img_metas, gt_bboxes,
+        gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None); the proposal list slices by count and SYNCHRONISES."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('forward_train')
+        return self._forward_train(*args, **kwargs)
+
+    def _forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        outs = self(x)
+        losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas=img_metas, cfg=proposal_cfg)
 
 
 def build_head(cfg):

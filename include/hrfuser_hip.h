@@ -492,6 +492,64 @@ int hrf_nms_segments(const float* cand, const int* valid, const int* seg_len, in
 int hrf_rpn_proposals(const hrf_rpn_levels_t* lv, const hrf_rpn_cfg_t* cfg, const float* img_shape, void* workspace,
                       long workspace_bytes, float* dets, int* count, float* rois, void* stream);
 
+/* ---- RPN training targets and loss (csrc/hrf_rpn_train.h, part of csrc/pointwise.hip) --------------------------------------------
+ * What RPNHead.loss does with the head's two maps per level and the ground-truth boxes (mmdet/core/anchor/anchor_generator.py:
+ * 392-451, core/anchor/utils.py:21-47, core/bbox/iou_calculators/iou2d_calculator.py:213-253, core/bbox/assigners/
+ * max_iou_assigner.py:128-213, core/bbox/samplers/base_sampler.py:83-98 + random_sampler.py:64-82, models/dense_heads/
+ * anchor_head.py:239-283 / :383-384 / :402-450 / :498-520, core/bbox/coder/delta_xywh_bbox_coder.py:118-160, rpn_head.py:70-101):
+ * inside flags, MaxIoUAssigner (gt_max_assign_all), a random sampler, BCE-with-logits + SmoothL1 and their gradients on the maps.
+ * Fixed-shape outputs, no host read of an input, no allocation, no synchronisation, no float atomics (the same bits in
+ * deterministic mode and from run to run), every loop bounded by a map size, Gmax or eight radix passes - capturable in a
+ * hipGraph.  Boxes, logits and deltas are unvalidated device data and may be NaN / Inf.
+ *   lv         the maps and anchors of the proposal entries above, read in place at their pitch.  The anchors of an image form
+ *              ONE list of N = sum_l H_l W_l A entries: level l at sum_{j<l} N_j, then (y * W + x) * A + a;
+ *   img_shape  [B][2] fp32 (h, w) for the inside flags; pad_shape [B][2] fp32 (h, w) for the valid flags
+ *              (valid_h = min(ceil(pad_h / stride), H)); both read at run time;
+ *   gt         [B][Gmax][4] fp32 (x1, y1, x2, y2); gt_count [B] int32, clamped to [0, Gmax] in the kernel; both read at run time:
+ *              a captured graph follows changed contents.  1 <= Gmax <= HRF_RPN_MAX_GT;
+ *   cfg        pos_iou_thr, neg_iou_thr, min_pos_iou in [0, 1]; match_low_quality 0 / 1; allowed_border (< 0: valid flags alone);
+ *              num >= 1 samples per image of which at most num_pos (0 .. num) positives; SmoothL1 beta > 0; the two loss weights;
+ *   keys       [B][N] uint32 sampling keys, or null: key = hash(rng_state[0] = seed, rng_state[1] = counter, image, n), the
+ *              32-bit integer hash written out in csrc/hrf_rpn_train.h.  The sampled positives (negatives) of an image are the
+ *              num_pos' = min(P, num_pos) (min(Q, num - num_pos')) assigned positives (negatives) of smallest (key, n): a uniform
+ *              subset - the reference's distribution, not its randperm stream.  With null keys hrf_rpn_loss advances the
+ *              counter in its last launch (a replayed graph draws fresh samples); hrf_rpn_assign never does;
+ *   assigned   [B][N] int32: -2 not inside, -1 ignored, 0 negative, i + 1 matched to gt i;  max_iou [B][N] fp32 (0 when not inside);
+ *   sampled    [B][N] int32: +1 sampled positive, -1 sampled negative, 0 neither;
+ *   counts     [B][4] int32: assigned positives, assigned negatives, sampled positives, sampled negatives;
+ *   grads      d_cls[l] / d_reg[l]: NHWC fp32 [B][H_l][W_l] rows of pitch ld_cls_l >= A / ld_reg_l >= 4 A; the A resp. 4 A leading
+ *              floats of EVERY row are written (zero off-sample, no memset needed): d loss_cls_l / d cls and d loss_bbox_l / d reg
+ *              with both loss weights and 1 / avg applied, avg = sum_b max(sampled pos_b, 1) + max(sampled neg_b, 1);
+ *   losses     [2][num_levels] fp32: loss_cls per level, then loss_bbox per level (sum of the weighted terms / avg * loss weight);
+ *   workspace  caller-owned device memory of hrf_rpn_train_workspace_bytes bytes, 256-byte aligned, contents irrelevant.
+ * hrf_rpn_assign = everything up to `sampled` (five launches); hrf_rpn_loss = everything (six).  hrf_rpn_train_supported -> 1 / 0,
+ * hrf_rpn_train_workspace_bytes -> 0 for what is refused.  REFUSED with HRF_ERR_ARG before any launch: A, num_levels, B, H, W,
+ * stride, the map pointers and pitches as for the proposal entries; N >= 2^30; Gmax outside [1, HRF_RPN_MAX_GT]; a threshold
+ * outside [0, 1] or NaN; num < 1; num_pos outside [0, num]; |allowed_border| > 2^24; beta <= 0 or not finite; a loss weight that is
+ * not finite; a null img_shape / pad_shape / gt / gt_count / output; keys and rng_state both null; a null gradient map or a
+ * gradient pitch smaller than the row (hrf_rpn_loss); a workspace that is null or too small.                                   */
+#define HRF_RPN_MAX_GT 256
+typedef struct hrf_rpn_train_cfg {
+  float pos_iou_thr, neg_iou_thr, min_pos_iou;
+  int match_low_quality, allowed_border, num, num_pos;
+  float beta, loss_weight_cls, loss_weight_bbox;
+} hrf_rpn_train_cfg_t;
+typedef struct hrf_rpn_grads {
+  float* d_cls[HRF_RPN_MAX_LEVELS];
+  float* d_reg[HRF_RPN_MAX_LEVELS];
+  int ld_cls[HRF_RPN_MAX_LEVELS];
+  int ld_reg[HRF_RPN_MAX_LEVELS];
+} hrf_rpn_grads_t;
+int hrf_rpn_train_supported(const hrf_rpn_levels_t* lv, const hrf_rpn_train_cfg_t* cfg, int Gmax);
+long hrf_rpn_train_workspace_bytes(const hrf_rpn_levels_t* lv, const hrf_rpn_train_cfg_t* cfg, int Gmax);
+int hrf_rpn_assign(const hrf_rpn_levels_t* lv, const hrf_rpn_train_cfg_t* cfg, const float* img_shape, const float* pad_shape,
+                   const float* gt, const int* gt_count, int Gmax, const unsigned* keys, unsigned* rng_state, void* workspace,
+                   long workspace_bytes, int* assigned, float* max_iou, int* sampled, int* counts, void* stream);
+int hrf_rpn_loss(const hrf_rpn_levels_t* lv, const hrf_rpn_train_cfg_t* cfg, const float* img_shape, const float* pad_shape,
+                 const float* gt, const int* gt_count, int Gmax, const unsigned* keys, unsigned* rng_state, void* workspace,
+                 long workspace_bytes, int* assigned, float* max_iou, int* sampled, int* counts, const hrf_rpn_grads_t* grads,
+                 float* losses, void* stream);
+
 /* ---- Cascade bbox head at test time (csrc/hrf_fc.h in csrc/conv3w_engine.hip; csrc/hrf_bbox.h in csrc/pointwise.hip) ----------
  * What CascadeRoIHead.simple_test does after RoIAlign (mmdet/models/roi_heads/cascade_roi_head.py:288-400, bbox_heads/
  * bbox_head.py:316-378 / :460-497, convfc_bbox_head.py, core/post_processing/bbox_nms.py:8-95, delta_xywh_bbox_coder.py:224-260):

@@ -19,7 +19,8 @@ extern "C" {
  * elementwise kernels; 19 = 1: hrf_fuse_sum through its per-element kernel), 24..27 conv3w_engine.hip, 28..31 lin2_engine.hip,
  * 36 = wave-group form of hrf_attn_block_fwd (0 = the dispatcher's choice, 1 / 2 / 4 = that many groups of four waves per window;
  * a launch of a width that is not built for the forced form returns HRF_ERR_ARG), 37 = a QUERY, not a status: returns the form a
- * forward of width `value` takes now (0: the forced form is not built for it). */
+ * forward of width `value` takes now (0: the forced form is not built for it), 44 = hrf_rpn_assign / hrf_rpn_loss return after
+ * their first `value` launches (1..6; 0 = all: incomplete outputs - tools/rpn_loss_cost.py times the launches one by one). */
 int hrf_debug_knob(int key, int value);
 
 /* hrf_debug_knob(7, 1): HIP-event durations of the grouped weight-gradient launches of eager steps, aggregated per kernel
