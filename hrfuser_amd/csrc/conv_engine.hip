@@ -1170,7 +1170,9 @@ extern "C" __attribute__((visibility("hidden"))) int hrf_w3x_knob(int key, int v
 extern "C" __attribute__((visibility("hidden"))) int hrf_dw_knob(int key, int value);
 extern "C" __attribute__((visibility("hidden"))) int hrf_ab_knob(int key, int value);
 extern "C" __attribute__((visibility("hidden"))) int hrf_rpnt_knob(int key, int value);
+extern "C" __attribute__((visibility("hidden"))) int hrf_bbt_knob(int key, int value);
 extern "C" int hrf_debug_knob(int key, int value) {
+  if (key >= 48 && key < 52) return hrf_bbt_knob(key - 48, value);     // hrf_bbox_train.h: 48 = return after launch `value` of a stage (1: of hrf_bbox_targets, 3: of hrf_bbox_loss; 0: all)
   if (key >= 44 && key < 48) return hrf_rpnt_knob(key - 44, value);    // hrf_rpn_train.h: 44 = return after the first `value` launches of hrf_rpn_assign / hrf_rpn_loss (0: all)
   if (key >= 36 && key < 40) return hrf_ab_knob(key - 36, value);      // attn_block.hip: 36 = wave-group form of the forward (0 auto, 1 / 2 / 4), 37 = query the form of width `value`
   if (key >= 40 && key < 44) return hrf_dw_knob(key - 40, value);      // dwconv.hip: 40 = float4-lane kernels (1 off, 2 / 3 tile height), 41 = grid threshold

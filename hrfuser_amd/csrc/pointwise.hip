@@ -2115,3 +2115,6 @@ extern "C" int hrf_memset(void* ptr, int value, long bytes, void* stream) {
 
 // RPN training targets and loss (inside flags, MaxIoUAssigner, sampler, BCE + SmoothL1 and their gradients): hrf_rpn_assign / hrf_rpn_loss
 #include "hrf_rpn_train.h"
+
+// cascade RoI head training targets and loss (assigner, sampler, bbox2delta, softmax CE + SmoothL1 + accuracy and their gradient): hrf_bbox_targets / hrf_bbox_loss
+#include "hrf_bbox_train.h"

@@ -94,6 +94,39 @@ class FeatureExtractor(nn.Module):
             img_metas = [dict(img_shape=tuple(img.shape[-2:]), pad_shape=tuple(img.shape[-2:]))] * img.shape[0]
         return self.rpn_head.loss(*self.rpn_head(x), gt_bboxes, img_metas)
 
+    def _roi_losses(self, x, outs, img, gt_bboxes, gt_labels, img_metas, proposal_cfg):
+        if getattr(self, 'roi_head', None) is None or getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor.roi_loss: built without an rpn_head / roi_head')
+        from .rpn import _shapes
+        shp = _shapes([m['img_shape'] for m in img_metas], img.shape[0], x[0].device)
+        _, count, rois = self.rpn_head.proposals(*outs, shp, proposal_cfg)
+        return self.roi_head.forward_train(x, img_metas, (rois, count), gt_bboxes, gt_labels)
+
+    def roi_loss(self, img, gt_bboxes, gt_labels, img_metas=None, lidar_img=None, radar_img=None, gated_img=None, proposal_cfg=None):
+        """extract_feat -> RPNHead.proposals -> CascadeRoIHead.forward_train (two_stage.py:163-177 without the RPN's own loss): mmdet's
+        dict s{i}.loss_cls / s{i}.acc / s{i}.loss_bbox.  The proposals stay in their fixed shape (rois, count): nothing synchronises.
+        gt_bboxes / gt_labels: lists per image; img_metas None: every image has the padded input size; proposal_cfg: train_cfg.rpn_proposal
+        (None: the RPN head's test_cfg)."""
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        if img_metas is None:
+            img_metas = [dict(img_shape=tuple(img.shape[-2:]), pad_shape=tuple(img.shape[-2:]))] * img.shape[0]
+        if getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor.roi_loss: built without an rpn_head')
+        return self._roi_losses(x, self.rpn_head(x), img, gt_bboxes, gt_labels, img_metas, proposal_cfg)
+
+    def losses(self, img, gt_bboxes, gt_labels, img_metas=None, lidar_img=None, radar_img=None, gated_img=None, proposal_cfg=None):
+        """two_stage.py:163-177: the RPN's dict (loss_rpn_cls / loss_rpn_bbox per level) and the RoI head's (s{i}.*) merged, from
+        ONE pass through the backbone, the neck and the RPN head."""
+        if getattr(self, 'rpn_head', None) is None:
+            raise ValueError('FeatureExtractor.losses: built without an rpn_head')
+        x = self.extract_feat(img, mod_imgs=combine_mod_imgs(lidar_img, radar_img, gated_img))
+        if img_metas is None:
+            img_metas = [dict(img_shape=tuple(img.shape[-2:]), pad_shape=tuple(img.shape[-2:]))] * img.shape[0]
+        outs = self.rpn_head(x)
+        out = dict(self.rpn_head.loss(*outs, gt_bboxes, img_metas))
+        out.update(self._roi_losses(x, outs, img, gt_bboxes, gt_labels, img_metas, proposal_cfg))
+        return out
+
     def extract_roi_feats(self, img, rois=None, lidar_img=None, radar_img=None, gated_img=None, img_shapes=None):
         """extract_feat followed by the RoI extractor (standard_roi_head.py:116-118: `bbox_roi_extractor(x[:num_inputs],
         rois)`): rois (K,5) = (batch index, x1, y1, x2, y2) -> (K, out_channels, 7, 7).  rois None: the `rois` of the RPN head

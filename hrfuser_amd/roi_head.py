@@ -3,7 +3,9 @@ reference config (configs/_base_/models/cascade_rcnn_hrfuser_fpn_*_fusion.py:148
 
 Drop-ins for mmdet's `Shared2FCBBoxHead` (mmdet/models/roi_heads/bbox_heads/convfc_bbox_head.py, bbox_head.py) and
 `CascadeRoIHead` (cascade_roi_head.py:288-400): same registry names, constructor keywords and state-dict keys
-(`bbox_head.{i}.shared_fcs.{0,1}.*`, `fc_cls.*`, `fc_reg.*`).  Eval / forward only, fp32, no tape: `loss` / `forward_train` raise.
+(`bbox_head.{i}.shared_fcs.{0,1}.*`, `fc_cls.*`, `fc_reg.*`).  The forward is eval only, fp32, no tape; with a `train_cfg` (a list of
+one train_cfg.rcnn dict per stage) the RoI head computes mmdet's per-stage losses and their gradient on each stage's head output,
+without one `loss` / `get_targets` / `forward_train` raise.
 
   Shared2FCBBoxHead.forward   fc1 and fc2 through hrf_fc (bias and ReLU in the launch, csrc/hrf_fc.h); fc_cls and fc_reg as ONE
                padded GEMM (the same entry, no activation) into a buffer of ceil16(num_classes + 5) columns - cls and reg are
@@ -16,7 +18,14 @@ Drop-ins for mmdet's `Shared2FCBBoxHead` (mmdet/models/roi_heads/bbox_heads/conv
                read, no synchronisation: capturable in a hipGraph.
   CascadeRoIHead.simple_test  mmdet's return type - bbox2result lists - which slices by `count` and therefore SYNCHRONISES.
 
-Functional entries underneath: `fc`, `bbox_refine`, `bbox_detect`.  There is no CPU fallback.
+  CascadeRoIHead.losses       per stage hrf_bbox_targets (MaxIoUAssigner without low-quality matching, the gts added as proposals,
+               RandomSampler, bbox2delta / stds; two launches, csrc/hrf_bbox_train.h) -> hrf_roi_align_fwd -> the head ->
+               hrf_bbox_loss (softmax CE, SmoothL1, top-1 accuracy and the gradient rows; two launches) -> hrf_bbox_refine.  The
+               sampled rows of an image are its sampled gts, then its other positives, then its negatives, then padding, so the next
+               stage's proposals - the refined rows without the gts - are a row range read from the device `counts`.  Fixed shapes, no
+               host read: capturable.  `forward_train` wraps it into mmdet's dict; `Shared2FCBBoxHead.loss` gives the values a grad_fn.
+
+Functional entries underneath: `fc`, `bbox_refine`, `bbox_detect`, `bbox_targets`, `bbox_loss`.  There is no CPU fallback.
 """
 import os
 
@@ -26,7 +35,7 @@ import torch.nn as nn
 from . import _lib
 from .registry import HEADS, ROI_EXTRACTORS
 from .roi import POOLED, _nhwc, roi_forward
-from .rpn import MAX_PRE, _shapes
+from .rpn import MAX_GT, MAX_PRE, _shapes, pack_gts, rng_state
 
 MAX_CLASSES = _lib._header_int('HRF_BBOX_MAX_CLASSES', 16)
 MAX_STAGES = _lib._header_int('HRF_BBOX_MAX_STAGES', 4)
@@ -164,6 +173,138 @@ def bbox_detect(rois, count, logits, deltas, stds, img_shapes, B, num_classes, s
     cnt = torch.empty((B,), device=dev, dtype=torch.int32)
     L.hrf_bbox_detect(d, workspace, workspace.numel(), dets, labels, cnt, _stream(stream))
     return dets, labels, cnt
+
+
+# ----------------------------------------------------------------------------- training targets and loss (csrc/hrf_bbox_train.h)
+def rcnn_train_cfg_struct(pos_iou_thr=0.5, neg_iou_thr=0.5, min_pos_iou=0.5, add_gt_as_proposals=True, num=512, num_pos=128, num_classes=80,
+                          stds=(0.1, 0.1, 0.2, 0.2), beta=1.0, loss_weight_cls=1.0, loss_weight_bbox=1.0):
+    """hrf_bbox_train_cfg_t of one stage; num_pos = int(num * pos_fraction); the loss weights include the stage's loss weight"""
+    c = _lib.BboxTrainCfg()
+    c.pos_iou_thr, c.neg_iou_thr, c.min_pos_iou = float(pos_iou_thr), float(neg_iou_thr), float(min_pos_iou)
+    c.add_gt_as_proposals, c.num, c.num_pos, c.num_classes = int(bool(add_gt_as_proposals)), int(num), int(num_pos), int(num_classes)
+    for k in range(4):
+        c.stds[k] = float(stds[k])
+    c.beta, c.loss_weight_cls, c.loss_weight_bbox = float(beta), float(loss_weight_cls), float(loss_weight_bbox)
+    return c
+
+
+def pack_gt_labels(gt_labels, dev, gmax):
+    """list of (n_i,) labels -> (B, gmax) int32 on `dev`, the companion of rpn.pack_gts (zeros past n_i; nothing synchronises)"""
+    out = torch.zeros((len(gt_labels), int(gmax)), device=dev, dtype=torch.int32)
+    for b, t in enumerate(gt_labels):
+        if t.shape[0]:
+            out[b, :t.shape[0]] = t.detach().reshape(-1).to(device=dev, dtype=torch.int32)
+    return out
+
+
+def _i32(t, shape, dev, what):
+    if t.shape != shape or t.dtype != torch.int32 or t.device != dev:
+        raise ValueError(f'{what} must be int32 {tuple(shape)} on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}')
+    return t
+
+
+def _refused(cfg, B, R, gmax):
+    return NotImplementedError(f'bbox targets on the HIP engine: R {R} (1..{MAX_PRE}), Gmax {gmax} (1..{MAX_GT}), num {cfg.num} (1..{MAX_PRE}), num_pos '
+                               f'{cfg.num_pos} in [0, num], num_classes {cfg.num_classes} (1..{MAX_CLASSES}), thresholds ({cfg.pos_iou_thr}, '
+                               f'{cfg.neg_iou_thr}, {cfg.min_pos_iou}) in [0, 1], stds {list(cfg.stds)} > 0, beta {cfg.beta} > 0, finite loss '
+                               f'weights or B {B} are not supported')
+
+
+def bbox_targets(rois, gt, gt_labels, gt_count, cfg, first=None, count=None, keys=None, rng=None, stage=0, stream=None):
+    """hrf_bbox_targets: rois (B*R,5) fp32, image b at rows b*R..; gt (B,Gmax,4) / gt_count (B,) from rpn.pack_gts, gt_labels (B,Gmax)
+    int32 (pack_gt_labels); cfg: rcnn_train_cfg_struct(...); first / count: int32 (B,) views of ONE stride (two columns of an earlier
+    stage's `counts` are read in place) or None; keys (B,Gmax+R) int32 (uint32 values) or rng = rpn.rng_state(seed, counter) (never
+    advanced here) -> (rois_s (B*num,5), labels (B*num,) int32, bbox_targets (B*num,4), src (B*num,) int32, counts (B,6) int32,
+    assigned (B,Gmax+R) int32, max_iou (B,Gmax+R) fp32)"""
+    L = _lib.lib()
+    dev = rois.device
+    if gt.dim() != 3 or gt.shape[2] != 4 or gt.dtype != torch.float32 or not gt.is_contiguous() or gt.device != dev:
+        raise ValueError(f'bbox_targets: gt must be contiguous fp32 (B, Gmax, 4) on {dev}, got {tuple(gt.shape)} {gt.dtype} on {gt.device}')
+    B, gmax = gt.shape[0], gt.shape[1]
+    if rois.dim() != 2 or rois.shape[1] != 5 or rois.dtype != torch.float32 or not rois.is_contiguous() or rois.shape[0] % B != 0:
+        raise ValueError(f'bbox_targets: rois must be contiguous fp32 (B * R, 5), got {tuple(rois.shape)} {rois.dtype} for B = {B}')
+    R = rois.shape[0] // B
+    _i32(gt_count, (B,), dev, 'bbox_targets: gt_count')
+    if not _i32(gt_labels, (B, gmax), dev, 'bbox_targets: gt_labels').is_contiguous():
+        raise ValueError('bbox_targets: gt_labels must be contiguous')
+    rs = 1
+    for t, what in ((first, 'first'), (count, 'count')):
+        if t is not None:
+            _i32(t, (B,), dev, 'bbox_targets: ' + what)
+    strides = {max(int(t.stride(0)), 1) for t in (first, count) if t is not None and B > 1}
+    if len(strides) > 1:
+        raise ValueError('bbox_targets: first and count must share one stride')
+    if strides:
+        rs = strides.pop()
+    if keys is not None and (keys.shape != (B, gmax + R) or keys.dtype != torch.int32 or not keys.is_contiguous() or keys.device != dev):
+        raise ValueError(f'bbox_targets: keys must be contiguous int32 ({B}, {gmax + R}) holding uint32 values on {dev}, got {tuple(keys.shape)} {keys.dtype}')
+    if keys is None and (rng is None or rng.shape != (2,) or rng.dtype != torch.int32 or rng.device != dev):
+        raise ValueError(f'bbox_targets: without keys an int32 (2,) rng_state (seed, counter) on {dev} is needed (rpn.rng_state)')
+    if L.require_cuda and not rois.is_cuda:
+        raise _lib.HRFuserHipError(f'bbox_targets: tensor on {dev}; the HIP path has no CPU fallback')
+    if not L.hrf_bbox_train_supported(cfg, B, R, gmax):
+        raise _refused(cfg, B, R, gmax)
+    n = B * cfg.num
+    outs = (torch.empty((n, 5), device=dev, dtype=torch.float32), torch.empty((n,), device=dev, dtype=torch.int32),
+            torch.empty((n, 4), device=dev, dtype=torch.float32), torch.empty((n,), device=dev, dtype=torch.int32),
+            torch.empty((B, 6), device=dev, dtype=torch.int32), torch.empty((B, gmax + R), device=dev, dtype=torch.int32),
+            torch.empty((B, gmax + R), device=dev, dtype=torch.float32))
+    L.hrf_bbox_targets(cfg, B, R, rois, first, count, rs, gt, gt_labels, gt_count, gmax, keys, rng, int(stage), *outs, _stream(stream))
+    return outs
+
+
+def bbox_loss(out, labels, targets, counts, cfg, rng=None, d_out=None, losses=None, workspace=None, stream=None):
+    """hrf_bbox_loss: out (B*num, >= num_classes + 5) fp32 rows of one pitch (the padded head output), labels / targets / counts of
+    bbox_targets -> (losses (3,) fp32 = loss_cls, loss_bbox, acc; d_out (B*num, ceil16(num_classes + 5)): d (loss_cls + loss_bbox) /
+    d out - the dY of the fused fc_cls / fc_reg GEMM).  rng: the rng_state whose counter this call advances (the last stage of a
+    step), or None.  d_out / losses: buffers to write into instead of new ones."""
+    L = _lib.lib()
+    dev, B = out.device, counts.shape[0]
+    n, P = B * cfg.num, _ceil16(cfg.num_classes + 5)
+    if out.dim() != 2 or out.shape[0] != n or out.shape[1] < cfg.num_classes + 5 or out.dtype != torch.float32 or out.stride(1) != 1:
+        raise ValueError(f'bbox_loss: out must be fp32 ({n}, >= {cfg.num_classes + 5}) rows, got {tuple(out.shape)} {out.dtype}')
+    _i32(labels, (n,), dev, 'bbox_loss: labels')
+    _i32(counts, (B, 6), dev, 'bbox_loss: counts')
+    if targets.shape != (n, 4) or targets.dtype != torch.float32 or not targets.is_contiguous() or not labels.is_contiguous() or not counts.is_contiguous():
+        raise ValueError(f'bbox_loss: contiguous labels ({n},), targets fp32 ({n}, 4) and counts ({B}, 6) are needed')
+    if L.require_cuda and not out.is_cuda:
+        raise _lib.HRFuserHipError(f'bbox_loss: tensor on {dev}; the HIP path has no CPU fallback')
+    need = L.hrf_bbox_train_workspace_bytes(cfg, B, 1, 1)
+    if need == 0:
+        raise _refused(cfg, B, 1, 1)
+    if workspace is None:
+        workspace = torch.empty((need,), device=dev, dtype=torch.uint8)
+    if d_out is None:
+        d_out = torch.empty((n, P), device=dev, dtype=torch.float32)
+    if d_out.shape[0] != n or d_out.shape[1] < P or d_out.dtype != torch.float32 or d_out.stride(1) != 1 or d_out.device != dev:
+        raise ValueError(f'bbox_loss: d_out must be fp32 ({n}, >= {P}) rows on {dev}, got {tuple(d_out.shape)} {d_out.dtype}')
+    if losses is None:
+        losses = torch.empty((3,), device=dev, dtype=torch.float32)
+    ld = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
+    ldd = d_out.stride(0) if n > 1 else max(d_out.stride(0), d_out.shape[1])
+    L.hrf_bbox_loss(cfg, B, out, ld, labels, targets, counts, workspace, workspace.numel(), d_out, ldd, losses, rng, _stream(stream))
+    return losses, d_out
+
+
+class _BboxLossFn(torch.autograd.Function):
+    """torch.autograd bridge of Shared2FCBBoxHead.loss: forward runs hrf_bbox_loss on a packed copy of (cls_score, bbox_pred) and
+    keeps the gradient rows; backward scales them by the incoming per-loss gradients.  The gradient of loss_cls lives in the logit
+    columns alone and that of loss_bbox in the delta columns alone, so one buffer serves both."""
+
+    @staticmethod
+    def forward(fctx, cfg, labels, targets, counts, cls_score, bbox_pred):
+        nc = cfg.num_classes
+        out = torch.zeros((cls_score.shape[0], _ceil16(nc + 5)), device=cls_score.device, dtype=torch.float32)
+        out[:, :nc + 1], out[:, nc + 1:nc + 5] = cls_score.detach().float(), bbox_pred.detach().float()
+        losses, d = bbox_loss(out, labels, targets, counts, cfg)
+        fctx.hrf = (d, nc)
+        return losses
+
+    @staticmethod
+    def backward(fctx, gl):
+        d, nc = fctx.hrf
+        gl = gl.float()
+        return None, None, None, None, d[:, :nc + 1] * gl[0], d[:, nc + 1:nc + 5] * gl[1]
 
 
 def _not_built(who, key, value, why):
@@ -319,12 +460,59 @@ class Shared2FCBBoxHead(nn.Module):
             out = self.run(x.detach().contiguous().reshape(x.shape[0], -1), nhwc=layout == 'nhwc')
         return out[:, :nc + 1], out[:, nc + 1:nc + 5]
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError('Shared2FCBBoxHead on the HIP engine: loss is not built - assigners, samplers and losses are out of scope; '
-                                  'the head is forward only')
+    def _no_train_cfg(self, what):
+        return NotImplementedError(f'Shared2FCBBoxHead on the HIP engine: {what} is not built without a train_cfg - assigners, samplers and losses are '
+                                   'named by the train_cfg of the CascadeRoIHead that owns the head; this head is forward only')
+
+    def _stage_cfg(self, n=None):
+        """the hrf_bbox_train_cfg_t of the owning stage; n: one `image` of n rows (the rows of a whole batch, mmdet's loss signature)"""
+        kw = dict(self.__dict__['_rcnn_train'])
+        if n is not None:
+            kw.update(num=n, num_pos=min(kw['num_pos'], n))
+        return rcnn_train_cfg_struct(**kw)
 
     def get_targets(self, *args, **kwargs):
-        raise NotImplementedError('Shared2FCBBoxHead on the HIP engine: get_targets is not built - training is out of scope')
+        """bbox_head.py:187-255 on the fixed-shape sampling results of this engine.  Signature (sampling_results, gt_bboxes, gt_labels,
+        rcnn_train_cfg=None, concat=True); sampling_results: what `bbox_targets` returned for the stage (the kernel has encoded the
+        targets already; gt_bboxes / gt_labels are not read again) -> (labels (B*num,) int64 with num_classes on the padding, as a
+        zero label weight makes it irrelevant, label_weights, bbox_targets (B*num,4), bbox_weights (B*num,4))"""
+        if '_rcnn_train' not in self.__dict__:
+            raise self._no_train_cfg('get_targets')
+        return self._get_targets(*args, **kwargs)
+
+    def _get_targets(self, sampling_results, gt_bboxes=None, gt_labels=None, rcnn_train_cfg=None, concat=True):
+        if not concat:
+            raise _not_built('Shared2FCBBoxHead', 'get_targets concat', concat, 'the kernels keep the rows of a batch in one buffer')
+        if not isinstance(sampling_results, (tuple, list)) or len(sampling_results) != 7 or not isinstance(sampling_results[1], torch.Tensor):
+            raise _not_built('Shared2FCBBoxHead', 'get_targets sampling_results', type(sampling_results).__name__,
+                             'the tuple roi_head.bbox_targets returns; mmdet SamplingResult objects are not')
+        _, labels, targets = sampling_results[:3]
+        nc = self.num_classes
+        lw = (labels >= 0).float()
+        bw = ((labels >= 0) & (labels < nc)).float()[:, None].expand(-1, 4)
+        return torch.where(labels >= 0, labels, torch.full_like(labels, nc)).long(), lw, targets, bw
+
+    def loss(self, *args, **kwargs):
+        """bbox_head.py:257-313 -> dict(loss_cls, acc, loss_bbox) with a grad_fn: backward delivers the kernel's gradient, scaled by
+        the incoming gradients, to cls_score / bbox_pred.  Signature (cls_score (n, num_classes + 1), bbox_pred (n, 4), rois, labels,
+        label_weights, bbox_targets, bbox_weights, reduction_override=None); n <= HRF_RPN_MAX_PRE rows.  A zero label weight marks
+        a padding row; the other weights are what get_targets gives (1 / positives), they are not read again."""
+        if '_rcnn_train' not in self.__dict__:
+            raise self._no_train_cfg('loss')
+        return self._loss(*args, **kwargs)
+
+    def _loss(self, cls_score, bbox_pred, rois, labels, label_weights, bbox_targets, bbox_weights, reduction_override=None):
+        if reduction_override is not None:
+            raise _not_built('Shared2FCBBoxHead', 'loss reduction_override', reduction_override, 'mean, the default')
+        n, nc, dev = int(cls_score.shape[0]), self.num_classes, cls_score.device
+        if not 1 <= n <= MAX_PRE or tuple(cls_score.shape) != (n, nc + 1) or tuple(bbox_pred.shape) != (n, 4):
+            raise _not_built('Shared2FCBBoxHead', 'loss rows', (tuple(cls_score.shape), tuple(bbox_pred.shape)),
+                             f'(n, {nc + 1}) logits and (n, 4) class-agnostic deltas with 1 <= n <= {MAX_PRE}')
+        lab = torch.where(label_weights > 0, labels, torch.full_like(labels, -1)).to(device=dev, dtype=torch.int32).contiguous()
+        counts = torch.zeros((1, 6), device=dev, dtype=torch.int32)
+        counts[0, 5:6] = (lab >= 0).sum().to(torch.int32)           # the average factor, counted on the device: nothing synchronises
+        losses = _BboxLossFn.apply(self._stage_cfg(n), lab, bbox_targets.detach().float().contiguous().to(dev), counts, cls_score, bbox_pred)
+        return dict(loss_cls=losses[0], acc=losses[2], loss_bbox=losses[1])
 
 
 def _rcnn_cfg(cfg):
@@ -373,6 +561,10 @@ class CascadeRoIHead(nn.Module):
                 raise _not_built(who, 'bbox_head num_classes', [b.num_classes for b in self.bbox_head], 'one class count for all stages')
         if test_cfg is not None:
             _rcnn_cfg(test_cfg)                                    # an unsupported nms raises at build time
+        if train_cfg is not None:                                  # an unsupported assigner / sampler / loss raises at build time
+            self.__dict__['_stage_train'] = self._rcnn_train_cfg(train_cfg, self.bbox_head, self.stage_loss_weights)
+            for h, kw in zip(self.bbox_head, self._stage_train):
+                h.__dict__['_rcnn_train'] = kw
         self.fp16_enabled = False
 
     with_bbox, with_mask, with_shared_head = True, False, False
@@ -442,10 +634,152 @@ class CascadeRoIHead(nn.Module):
     def aug_test(self, *args, **kwargs):
         raise NotImplementedError('CascadeRoIHead on the HIP engine: aug_test is not built (out of scope)')
 
-    def loss(self, *args, **kwargs):
-        raise NotImplementedError('CascadeRoIHead on the HIP engine: loss is not built - assigners, samplers and losses (train_cfg) are out '
-                                  'of scope; the head is detect / simple_test only')
+    # -- training: targets and losses (csrc/hrf_bbox_train.h) ---------------------------------------------
+    @staticmethod
+    def _rcnn_train_cfg(train_cfg, heads, stage_loss_weights):
+        """-> per stage the keywords of rcnn_train_cfg_struct for train_cfg.rcnn (a list of dicts, one per stage) + the stage's head
+        and loss weight; anything the kernels do not build raises NotImplementedError naming the key"""
+        who = 'CascadeRoIHead'
+        if not isinstance(train_cfg, (list, tuple)) or len(train_cfg) != len(heads):
+            raise _not_built(who, 'train_cfg', train_cfg if not isinstance(train_cfg, (list, tuple)) else f'{len(train_cfg)} entries',
+                             f'a list of one dict per stage ({len(heads)} stages)')
+        out = []
+        for i, (tc_, hd, sw) in enumerate(zip(train_cfg, heads, stage_loss_weights)):
+            tc, pre = dict(tc_), f'train_cfg[{i}].'
+            asg, smp = dict(tc.pop('assigner', {})), dict(tc.pop('sampler', {}))
+            if asg.pop('type', None) != 'MaxIoUAssigner':
+                raise _not_built(who, pre + 'assigner.type', tc_.get('assigner', {}).get('type'), 'MaxIoUAssigner in every HRFuser config')
+            pos, neg = asg.pop('pos_iou_thr', None), asg.pop('neg_iou_thr', None)
+            if isinstance(neg, (tuple, list)) or not isinstance(neg, (int, float)) or not isinstance(pos, (int, float)):
+                raise _not_built(who, pre + 'assigner.pos_iou_thr / neg_iou_thr', (pos, neg), 'two numbers; a (low, high) tuple for neg_iou_thr is not')
+            min_pos = float(asg.pop('min_pos_iou', 0.0))
+            if asg.pop('match_low_quality', True):
+                raise _not_built(who, pre + 'assigner.match_low_quality', True, 'False in every HRFuser config; the RPN kernels have the low-quality pass')
+            if asg.pop('ignore_iof_thr', -1) >= 0:
+                raise _not_built(who, pre + 'assigner.ignore_iof_thr', tc_['assigner']['ignore_iof_thr'], 'gt_bboxes_ignore is out of scope; -1 in every HRFuser config')
+            asg.pop('ignore_wrt_candidates', True)                      # (only read with ignore_iof_thr >= 0)
+            asg.pop('gt_max_assign_all', True)                          # (only read with match_low_quality)
+            if asg.pop('gpu_assign_thr', -1) != -1:
+                raise _not_built(who, pre + 'assigner.gpu_assign_thr', tc_['assigner']['gpu_assign_thr'], 'the assignment never leaves the device; -1')
+            if dict(asg.pop('iou_calculator', dict(type='BboxOverlaps2D'))) != dict(type='BboxOverlaps2D') or asg:
+                raise _not_built(who, pre + 'assigner keys', sorted(asg) or 'iou_calculator', 'unknown to the kernel')
+            if smp.pop('type', None) != 'RandomSampler':
+                raise _not_built(who, pre + 'sampler.type', tc_.get('sampler', {}).get('type'), 'RandomSampler in every HRFuser config; OHEM is out of scope')
+            num, frac = smp.pop('num', None), smp.pop('pos_fraction', None)
+            if not isinstance(num, int) or not 1 <= num <= MAX_PRE or frac is None or not 0.0 <= float(frac) <= 1.0:
+                raise _not_built(who, pre + 'sampler.num / pos_fraction', (num, frac), f'1 <= num <= {MAX_PRE} and 0 <= pos_fraction <= 1')
+            if smp.pop('neg_pos_ub', -1) >= 0:
+                raise _not_built(who, pre + 'sampler.neg_pos_ub', tc_['sampler']['neg_pos_ub'], '-1 in every HRFuser config')
+            add_gt = bool(smp.pop('add_gt_as_proposals', True))
+            if smp:
+                raise _not_built(who, pre + 'sampler keys', sorted(smp), 'unknown to the kernel')
+            if tc.get('pos_weight', -1) > 0:
+                raise _not_built(who, pre + 'pos_weight', tc['pos_weight'], '-1 in every HRFuser config')
+            if tc.get('debug', False):
+                raise _not_built(who, pre + 'debug', True, 'False')
+            lc, lb = dict(hd.loss_cls or {}), dict(hd.loss_bbox or {})
+            if lc.get('class_weight') is not None or lc.get('reduction', 'mean') != 'mean':
+                raise _not_built(who, f'bbox_head[{i}].loss_cls', hd.loss_cls, 'a softmax CrossEntropyLoss with mean reduction and no class_weight')
+            if lb.get('type') != 'SmoothL1Loss' or lb.get('reduction', 'mean') != 'mean' or not float(lb.get('beta', 1.0)) > 0:
+                raise _not_built(who, f'bbox_head[{i}].loss_bbox', hd.loss_bbox, 'a SmoothL1Loss with beta > 0 and mean reduction')
+            out.append(dict(pos_iou_thr=float(pos), neg_iou_thr=float(neg), min_pos_iou=min_pos, add_gt_as_proposals=add_gt, num=num,
+                            num_pos=int(num * float(frac)), num_classes=hd.num_classes, stds=hd.target_stds, beta=float(lb.get('beta', 1.0)),
+                            loss_weight_cls=float(lc.get('loss_weight', 1.0)) * float(sw), loss_weight_bbox=float(lb.get('loss_weight', 1.0)) * float(sw)))
+        return out
+
+    def _no_train_cfg(self, what):
+        return NotImplementedError(f'CascadeRoIHead on the HIP engine: {what} is not built without train_cfg - the assigners and samplers of the '
+                                   'stages are named there (train_cfg.rcnn); the head is detect / simple_test only')
+
+    def rng(self, device):
+        """the device (seed, counter) pair the samplers draw from (rpn.rng_state); `losses` advances the counter once per call"""
+        st = self.__dict__.get('_rng')
+        if st is None or st.device != torch.device(device):
+            st = self.__dict__['_rng'] = rng_state(int(torch.initial_seed()), 0, device)
+        return st
+
+    def losses(self, *args, **kwargs):
+        """All stages of cascade_roi_head.py:191-286 with fixed shapes.  Signature (x, rois, count, gt, gt_labels, gt_count, img_shapes,
+        stages=None, keys=None): x the pyramid; rois (B*R,5) / count (B,) int32 or None as `detect` takes them (RPNHead.proposals);
+        gt (B,Gmax,4) fp32, gt_labels (B,Gmax) int32, gt_count (B,) int32 on the device (rpn.pack_gts, pack_gt_labels); img_shapes a
+        device (B,2) tensor or a list -> (losses (num_stages, 3) fp32: loss_cls, loss_bbox (both with the stage weight), acc per
+        stage; [d_out (B*num, ceil16(num_classes + 5))] per stage: the gradient of the stage's two losses on its padded head output,
+        the dY of its fc_cls / fc_reg GEMM).  Per stage hrf_bbox_targets -> hrf_roi_align_fwd -> Shared2FCBBoxHead.run ->
+        hrf_bbox_loss -> hrf_bbox_refine; the next stage reads rows [sampled gts, n_b) of the refined rows in place.  No host read,
+        no synchronisation: capturable; a captured graph follows changed gt / gt_labels / gt_count / rois contents and the last
+        launch advances the counter of `rng`.  stages: a list that receives a dict per stage (rois, first, count, targets, out,
+        d_out, cfg); keys: per stage explicit sampling keys (B, Gmax + R_stage) int32 instead of the generated ones."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('losses')
+        return self._losses(*args, **kwargs)
+
+    loss = losses
+
+    def _losses(self, x, rois, count, gt, gt_labels, gt_count, img_shapes, stages=None, keys=None):
+        x = tuple(x)
+        B, dev = x[0].shape[0], x[0].device
+        rois = rois.detach().float().contiguous()
+        if rois.dim() != 2 or rois.shape[1] != 5 or rois.shape[0] % B != 0 or rois.shape[0] == 0:
+            raise ValueError(f'CascadeRoIHead.losses: rois must be (B * R, 5) with R >= 1, got {tuple(rois.shape)} for B = {B}')
+        shp = _shapes(img_shapes, B, dev)
+        nc, S = self.bbox_head[0].num_classes, self.num_stages
+        rng = None if keys is not None else self.rng(dev)
+        out_losses = torch.empty((S, 3), device=dev, dtype=torch.float32)
+        maps, grads, first = {}, [], None
+        with torch.no_grad():
+            for i in range(S):
+                ex, hd = self.bbox_roi_extractor[i], self.bbox_head[i]
+                n = ex.num_inputs
+                if n not in maps:
+                    if len(x) < n:
+                        raise ValueError(f'CascadeRoIHead: {n} strides, {len(x)} maps')
+                    maps[n] = [_nhwc(t) for t in x[:n]]
+                cfg = rcnn_train_cfg_struct(**self._stage_train[i])
+                t = bbox_targets(rois, gt, gt_labels, gt_count, cfg, first, count, keys=None if keys is None else keys[i], rng=rng, stage=i)
+                rois_s, labels, targets, _, counts = t[:5]
+                feat = roi_forward(maps[n], rois_s, ex._scales(), float(ex.finest_scale), 1)         # (B*num,7,7,C)
+                out = hd.run(feat.reshape(feat.shape[0], -1), nhwc=True)
+                _, d = bbox_loss(out, labels, targets, counts, cfg, rng=rng if i == S - 1 else None, losses=out_losses[i])
+                grads.append(d)
+                if stages is not None:
+                    stages.append(dict(rois=rois, first=first, count=count, targets=t, out=out, d_out=d, cfg=cfg))
+                if i < S - 1:
+                    rois = bbox_refine(rois_s, out[:, nc + 1:nc + 5], hd.target_stds, shp, B)
+                    first, count = counts[:, 4], counts[:, 5]      # the sampled gts lead every image: the pos_is_gt filter is a row range
+        return out_losses, grads
 
     def forward_train(self, *args, **kwargs):
-        raise NotImplementedError('CascadeRoIHead on the HIP engine: forward_train is not built - assigners, samplers and losses (train_cfg) '
-                                  'are out of scope; the head is detect / simple_test only')
+        """cascade_roi_head.py:191-286 -> mmdet's dict: s{i}.loss_cls, s{i}.acc, s{i}.loss_bbox (the stage weight on the two losses
+        only).  Signature (x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None); proposal_list: a
+        list of (n_i, >= 4) boxes per image, or the fixed-shape pair (rois (B*R,5), count (B,) int32) of RPNHead.proposals;
+        gt_bboxes / gt_labels: lists per image (packed without a synchronisation).  The head's forward is no_grad: the values carry
+        no grad_fn; `losses` returns the gradient buffers."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('forward_train')
+        return self._forward_train(*args, **kwargs)
+
+    def _forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None, stages=None):
+        if gt_bboxes_ignore is not None:
+            raise _not_built('CascadeRoIHead', 'gt_bboxes_ignore', 'given', 'ignore regions are out of scope')
+        if gt_masks is not None:
+            raise _not_built('CascadeRoIHead', 'gt_masks', 'given', 'mask heads are out of scope')
+        x = tuple(x)
+        dev = x[0].device
+        if isinstance(proposal_list, tuple) and len(proposal_list) == 2 and isinstance(proposal_list[0], torch.Tensor) and proposal_list[0].dim() == 2 \
+                and proposal_list[0].shape[1] == 5 and proposal_list[1].dim() == 1:
+            rois, count = proposal_list
+        else:
+            B = len(proposal_list)
+            R = max([int(p.shape[0]) for p in proposal_list] + [1])
+            rois = torch.zeros((B, R, 5), device=dev, dtype=torch.float32)
+            for b, p in enumerate(proposal_list):
+                rois[b, :, 0] = float(b)
+                rois[b, :p.shape[0], 1:] = p[:, :4].to(dev).float()
+            rois = rois.reshape(B * R, 5)
+            count = torch.tensor([int(p.shape[0]) for p in proposal_list], dtype=torch.int32).to(dev)
+        gt, gt_count = pack_gts(gt_bboxes, dev)
+        vals, _ = self.losses(x, rois, count, gt, pack_gt_labels(gt_labels, dev, gt.shape[1]), gt_count, [m['img_shape'] for m in img_metas], stages=stages)
+        out = {}
+        for i in range(self.num_stages):
+            out[f's{i}.loss_cls'], out[f's{i}.acc'], out[f's{i}.loss_bbox'] = vals[i, 0], vals[i, 2], vals[i, 1]
+        return out

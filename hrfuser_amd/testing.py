@@ -476,3 +476,133 @@ def rpn_loss_ref(cls_scores, bbox_preds, anchors, assigned, sampled, gts, beta=1
         out_b.append(loss_bbox.detach())
         off += n
     return out_c, out_b, g_c, g_b, tuple(arms)
+
+
+# ----------------------------------------------------------------------------- CascadeRoIHead.forward_train restatement
+# The oracle of hrfuser_amd.roi_head.bbox_targets / bbox_loss / CascadeRoIHead.losses (csrc/hrf_bbox_train.h; no mmcv / mmdet here:
+# parity against an installed mmdet is unpinned): literal torch restatements of max_iou_assigner.py:84-213 with
+# match_low_quality False, assign_result.py:196-206 (add_gt_), base_sampler.py:68-102 (the gts in FRONT of the proposals) +
+# random_sampler.py:64-82 with the random choice replaced by "the k smallest (key, index)", sampling_result.py (bboxes = cat(pos,
+# neg), positives and negatives each in ascending index), bbox_head.py:122-255 (get_targets) / :257-313 (loss) and
+# cascade_roi_head.py:191-286.  Candidates are in mmdet's compact order: the G gts (when added), then the proposals.  Everything
+# runs in `dtype` from fp32 inputs: fp32 is the reference's arithmetic, fp64 the yardstick of it.
+def _mix32(h):
+    M = 0xffffffff
+    h &= M
+    h ^= h >> 16
+    h = (h * 0x7feb352d) & M
+    h ^= h >> 15
+    h = (h * 0x846ca68b) & M
+    return h ^ (h >> 16)
+
+
+def rcnn_key_ref(seed, counter, stage, b, N):
+    """the generated sampling keys of image b in stage `stage` over the N = Gmax + R candidate slots (csrc/hrf_bbox_train.h):
+    the RPN's hash with the stage folded into the seed, rpn_key_ref(seed ^ mix(0x5bd1e995 + stage), counter, b, N)"""
+    return rpn_key_ref((int(seed) & 0xffffffff) ^ _mix32(0x5bd1e995 + int(stage)), counter, b, N)
+
+
+def rcnn_assign_ref(proposals, gts, pos_iou_thr, neg_iou_thr, add_gt_as_proposals=True, dtype=torch.float32):
+    """MaxIoUAssigner(match_low_quality=False).assign on ONE image's proposals (n,4) and gts (G,4), then add_gt_ ->
+    (assigned (G + n,) int64: -1 / 0 / i + 1, max_iou (G + n,), boxes (G + n, 4)); without add_gt_as_proposals the G leading
+    entries are absent.  A NaN IoU makes the column's maximum NaN (torch.max), which fails every comparison: -1."""
+    p, g = proposals.reshape(-1, 4).to(dtype), gts.reshape(-1, 4).to(dtype)
+    assigned, mx = max_iou_assign_ref(bbox_overlaps_ref(g, p), pos_iou_thr, neg_iou_thr, 0.0, False)
+    if not add_gt_as_proposals:
+        return assigned, mx, p
+    G = g.shape[0]
+    return torch.cat([torch.arange(1, G + 1, dtype=torch.long, device=assigned.device), assigned]), torch.cat([mx.new_ones(G), mx]), torch.cat([g, p])
+
+
+def rcnn_sample_ref(assigned, keys, num, num_pos):
+    """RandomSampler (neg_pos_ub -1) on ONE image given keys (one per candidate, uint32 values in int64) -> (pos_inds, neg_inds),
+    each ascending: the min(P, num_pos) positives and the min(Q, num - that) negatives of smallest (key, index)"""
+    s = rpn_sample_ref(assigned, keys, num, num_pos)
+    return torch.nonzero(s > 0)[:, 0], torch.nonzero(s < 0)[:, 0]
+
+
+def bbox_targets_ref(boxes, assigned, pos_inds, neg_inds, gts, gt_labels, num_classes, stds, dtype=torch.float32):
+    """bbox_head.py:122-185 (_get_target_single, pos_weight <= 0) on ONE image -> (rows (n,4) = cat(pos boxes, neg boxes),
+    labels (n,) int64, bbox_targets (n,4)): bbox2delta(pos box, its gt) / stds on the positives, zero on the negatives"""
+    bx, g = boxes.to(dtype), gts.reshape(-1, 4).to(dtype)
+    rows = torch.cat([bx[pos_inds], bx[neg_inds]])
+    labels = torch.full((rows.shape[0],), int(num_classes), dtype=torch.long, device=rows.device)
+    targets = torch.zeros((rows.shape[0], 4), dtype=dtype, device=rows.device)
+    npos = pos_inds.numel()
+    if npos:
+        m = assigned[pos_inds] - 1
+        labels[:npos] = gt_labels.long()[m]
+        targets[:npos] = rpn_bbox2delta_ref(bx[pos_inds], g[m]) / targets.new_tensor([float(s) for s in stds])
+    return rows, labels, targets
+
+
+def bbox_loss_ref(logits, deltas, labels, targets, num_classes, beta=1.0, loss_weight_cls=1.0, loss_weight_bbox=1.0, dtype=torch.float32):
+    """bbox_head.py:257-313 on the rows of the whole batch (labels in [0, num_classes]; label weights 1): F.cross_entropy summed /
+    max(n, 1), SmoothL1 on the positives summed / n (avg_factor = bbox_targets.size(0)), accuracy top-1 ->
+    dict(loss_cls, loss_bbox, acc, correct, d_logits, d_deltas, arms = SmoothL1 (quadratic, linear) counts)"""
+    import torch.nn.functional as F
+    x, d = logits.detach().to(dtype).requires_grad_(True), deltas.detach().to(dtype).requires_grad_(True)
+    n = int(labels.numel())
+    t = targets.to(dtype)
+    if n == 0:
+        z = torch.zeros((), dtype=dtype)
+        return dict(loss_cls=z, loss_bbox=z, acc=z, correct=0, d_logits=torch.zeros_like(x), d_deltas=torch.zeros_like(d), arms=(0, 0))
+    loss_cls = F.cross_entropy(x, labels.long(), reduction='none').sum() / float(max(n, 1)) * loss_weight_cls
+    pos = (labels >= 0) & (labels < num_classes)
+    diff = (d[pos] - t[pos]).abs()
+    l1 = torch.where(diff < beta, 0.5 * diff * diff / beta, diff - 0.5 * beta)
+    loss_bbox = l1.sum() / float(n) * loss_weight_bbox
+    correct = int((x.detach().argmax(dim=1) == labels).sum())
+    g_x = torch.autograd.grad(loss_cls, x)[0]
+    g_d = torch.autograd.grad(loss_bbox, d)[0] if bool(pos.any()) else torch.zeros_like(d)
+    return dict(loss_cls=loss_cls.detach(), loss_bbox=loss_bbox.detach(), acc=torch.tensor(100.0 * correct / n, dtype=dtype), correct=correct,
+                d_logits=g_x, d_deltas=g_d, arms=(int((diff < beta).sum()), int((~(diff < beta)).sum())))
+
+
+def cascade_forward_train_ref(feats, proposals, gts, gt_labels, img_shapes, sds, stage_cfgs, stds_per_stage, num_classes, strides, key_fn,
+                              finest_scale=56, dtype=torch.float32):
+    """CascadeRoIHead.forward_train (cascade_roi_head.py:191-286), bbox branch, class-agnostic regression.  feats: NCHW maps;
+    proposals [(n_b,4)], gts [(G_b,4)], gt_labels [(G_b,)] per image; sds: one mmdet state dict per stage; stage_cfgs: per stage
+    dict(pos_iou_thr, neg_iou_thr, num, num_pos, add_gt_as_proposals, beta, loss_weight_cls, loss_weight_bbox, stage_weight);
+    key_fn(stage, b, is_gt (m,) bool, index (m,) int64) -> (m,) int64 keys of the candidates (index: the gt number or the
+    proposal's position in the stage's list).  RoI features and the head run in `dtype`, the box arithmetic in fp32 ->
+    (losses: mmdet's dict s{i}.loss_cls / s{i}.acc / s{i}.loss_bbox, per-stage records dict(proposals, rois, labels, targets,
+    pos_is_gt, logits, deltas))"""
+    B = len(proposals)
+    props = [p.float().reshape(-1, 4) for p in proposals]
+    losses, records = {}, []
+    for i, (sd, sc) in enumerate(zip(sds, stage_cfgs)):
+        rows, labels, targets, is_gt = [], [], [], []
+        for b in range(B):
+            add = bool(sc.get('add_gt_as_proposals', True))
+            assigned, _, boxes = rcnn_assign_ref(props[b], gts[b], sc['pos_iou_thr'], sc['neg_iou_thr'], add)
+            G = gts[b].reshape(-1, 4).shape[0] if add else 0
+            m = boxes.shape[0]
+            gt_flag = torch.arange(m) < G
+            keys = key_fn(i, b, gt_flag, torch.where(gt_flag, torch.arange(m), torch.arange(m) - G))
+            pos, neg = rcnn_sample_ref(assigned, keys, sc['num'], sc['num_pos'])
+            r, l, t = bbox_targets_ref(boxes, assigned, pos, neg, gts[b], gt_labels[b], num_classes, stds_per_stage[i])
+            rows.append(torch.cat([torch.full((r.shape[0], 1), float(b)), r], dim=1))
+            labels.append(l)
+            targets.append(t)
+            is_gt.append(torch.cat([gt_flag[pos], torch.zeros(neg.numel(), dtype=torch.bool)]))
+        rois = torch.cat(rows)
+        x = roi_extract_ref([f.to(dtype) for f in feats], rois.to(dtype), strides, finest_scale)
+        cls, deltas = bbox_head_ref(x, sd)
+        w = float(sc.get('stage_weight', 1.0))
+        lr = bbox_loss_ref(cls.float(), deltas.float(), torch.cat(labels), torch.cat(targets), num_classes, sc.get('beta', 1.0),
+                           sc.get('loss_weight_cls', 1.0) * w, sc.get('loss_weight_bbox', 1.0) * w, dtype)
+        losses[f's{i}.loss_cls'], losses[f's{i}.acc'], losses[f's{i}.loss_bbox'] = lr['loss_cls'], lr['acc'], lr['loss_bbox']
+        records.append(dict(proposals=[p.clone() for p in props], rois=rois, labels=torch.cat(labels), targets=torch.cat(targets),
+                            pos_is_gt=is_gt, logits=cls.float(), deltas=deltas.float()))
+        if i < len(sds) - 1:                                        # refine_bboxes: regress every sampled row, drop the sampled gts
+            off, new = 0, []
+            for b in range(B):
+                n = rows[b].shape[0]
+                bx = bbox_delta2bbox(rois[off:off + n, 1:], deltas.float()[off:off + n], stds_per_stage[i], max_shape=img_shapes[b])
+                keep = torch.ones(n, dtype=torch.bool)
+                keep[:n] = ~is_gt[b]
+                new.append(bx[keep])
+                off += n
+            props = new
+    return losses, records

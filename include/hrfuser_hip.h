@@ -613,6 +613,76 @@ int hrf_bbox_refine(const float* rois_in, const float* deltas, int ld_deltas, fl
 long hrf_bbox_detect_workspace_bytes(int B, int R, int num_classes);
 int hrf_bbox_detect(const hrf_bbox_det_t* d, void* workspace, long workspace_bytes, float* dets, int* labels, int* count_out,
                     void* stream);
+
+/* ---- Cascade RoI head training targets and loss (csrc/hrf_bbox_train.h, part of csrc/pointwise.hip) -----------------------------
+ * One stage of train_cfg.rcnn[i]: what CascadeRoIHead.forward_train does per stage between the proposals and the loss values
+ * (mmdet/models/roi_heads/cascade_roi_head.py:191-286, bbox_heads/bbox_head.py:122-313, core/bbox/assigners/max_iou_assigner.py
+ * with match_low_quality False, assign_result.py add_gt_, samplers/base_sampler.py:68-102 + random_sampler.py with neg_pos_ub -1,
+ * iou2d_calculator.py:213-253, delta_xywh_bbox_coder.py:118-160, CrossEntropyLoss (softmax), SmoothL1Loss, accuracy top-1).
+ * Fixed-shape outputs, no host read of an input, no allocation, no synchronisation, no float atomics (the same bits in
+ * deterministic mode and from run to run), every loop bounded by Gmax, Gmax + R, num, num_classes or six radix passes - never by
+ * data: capturable in a hipGraph.  Boxes, labels, logits and deltas are unvalidated device data.
+ *
+ * hrf_bbox_targets (two launches): assignment, sampling, target encoding.
+ *   rois_in    [B * R][5] fp32 (b, x1, y1, x2, y2), image b at rows b * R ..; 1 <= R <= HRF_RPN_MAX_PRE;
+ *   first / count  row range [first_b, count_b) of image b: int32 read at first[b * range_stride] / count[b * range_stride] on the
+ *              device and clamped into [0, R]; either may be null (0 / R).  Rows outside the range are never read.  range_stride
+ *              >= 1 lets two columns of an earlier stage's `counts` serve (counts + 4, counts + 5, stride 6);
+ *   gt         [B][Gmax][4] fp32, gt_labels [B][Gmax] int32, gt_count [B] int32 clamped to [0, Gmax] in the kernel; read at run
+ *              time: a captured graph follows changed contents.  1 <= Gmax <= HRF_RPN_MAX_GT;
+ *   keys       [B][Gmax + R] uint32 sampling keys, or null: key = the hash of hrf_rpn_loss over (rng_state[0] ^ mix(0x5bd1e995 +
+ *              stage), rng_state[1], image, slot) - `stage` (0 .. 255) decorrelates the stages of a step from each other and
+ *              from the RPN.  hrf_bbox_targets never advances the counter.
+ * The candidates of image b are the slots c of ONE index space of Gmax + R: c < Gmax is ground truth c, valid iff
+ * add_gt_as_proposals != 0 and c < G_b; c = Gmax + r is row r, valid iff first_b <= r < count_b.  A ground-truth slot is assigned
+ * c + 1 with max_iou 1 (add_gt_).  A row takes the maximum of bbox_overlaps over the G_b ground truths in its fp32 order (ties:
+ * the first ground truth): max >= pos_iou_thr -> argmax + 1; 0 <= max < neg_iou_thr -> 0; otherwise -1.  G_b == 0: every row 0
+ * with max_iou 0.  NaN propagates as in torch.max / torch.min: a row with any NaN IoU has max_iou NaN, is assigned -1 and is never
+ * sampled.  The sampler keeps the min(P_b, num_pos) positives of smallest (key, c), then the min(N_b, num - sampled pos_b)
+ * negatives of smallest (key, c): a uniform subset - RandomSampler's distribution, not its randperm stream.  Outputs (every
+ * element of every output is written, no memset needed), image b at rows b * num ..:
+ *   rois_s     [B * num][5]: the sampled positives in ascending c, then the sampled negatives in ascending c, then padding rows
+ *              (b, 0, 0, 0, 0).  Sampled ground truths are therefore the first rows of an image, and rows [counts[b][4], counts[b][5])
+ *              are the sampled proposals: the next stage's range after hrf_bbox_refine (the reference's pos_is_gt filter);
+ *   labels     [B * num] int32: gt_labels of the matched ground truth / num_classes (negative) / -1 (padding);
+ *   bbox_targets [B * num][4]: bbox2delta(box, matched gt) / stds on the positives, zero elsewhere;
+ *   src        [B * num] int32: the candidate slot of the row, -1 for padding;
+ *   counts     [B][6] int32: P_b, N_b, sampled positives, sampled negatives, sampled ground truths, rows n_b;
+ *   assigned   [B][Gmax + R] int32 (-2: the slot is no candidate), max_iou [B][Gmax + R] fp32 (0 there).
+ *
+ * hrf_bbox_loss (two launches): the losses of those rows on the padded head output, and their gradient.
+ *   out        [B * num] rows of pitch ld >= num_classes + 5: num_classes + 1 logits (background last), then four deltas;
+ *   losses     [3] fp32, n = sum_b n_b (read on the device):
+ *              [0] loss_weight_cls * sum_rows CE(softmax, stable log-sum-exp) / max(n, 1)   (label weights 1),
+ *              [1] loss_weight_bbox * sum_{positive rows, 4} SmoothL1_beta(delta - target) / n   (0 when n == 0 or no positive),
+ *              [2] 100 * #(argmax of the logits == label, the lowest index wins a tie) / n   (0 when n == 0; no loss weight);
+ *   d_out      [B * num] rows of pitch ld_d: the ceil16(num_classes + 5) leading floats of EVERY row are written: d (losses[0] +
+ *              losses[1]) / d out, zero on padding rows, on rows whose label is outside [0, num_classes] and in the pad columns;
+ *   rng_state  nullable: when given, the last launch advances rng_state[1] (the caller passes it with the last stage of a step);
+ *   workspace  hrf_bbox_train_workspace_bytes bytes (one fp64 slot triple per 256 rows, folded in slot order), 256-byte aligned,
+ *              caller-owned, contents irrelevant.
+ * cfg: the loss weights already include the stage's loss weight; min_pos_iou is validated but unused (match_low_quality False).
+ * hrf_bbox_train_supported -> 1 / 0; hrf_bbox_train_workspace_bytes -> 0 for what is refused.  REFUSED with HRF_ERR_ARG before
+ * any launch: B outside [1, 65535]; R outside [1, HRF_RPN_MAX_PRE]; Gmax outside [1, HRF_RPN_MAX_GT]; num outside
+ * [1, HRF_RPN_MAX_PRE]; num_pos outside [0, num]; num_classes outside [1, HRF_BBOX_MAX_CLASSES]; a threshold outside [0, 1] or NaN;
+ * a std or beta that is not positive and finite; a loss weight that is not finite; range_stride < 1; stage outside [0, 255];
+ * ld < num_classes + 5; ld_d < ceil16(num_classes + 5); a null cfg / input / output (first, count, keys and the rng_state of
+ * hrf_bbox_loss excepted); keys and rng_state both null (hrf_bbox_targets); a workspace that is null or too small (hrf_bbox_loss). */
+typedef struct hrf_bbox_train_cfg {
+  float pos_iou_thr, neg_iou_thr, min_pos_iou;
+  int add_gt_as_proposals, num, num_pos, num_classes;
+  float stds[4];
+  float beta, loss_weight_cls, loss_weight_bbox;
+} hrf_bbox_train_cfg_t;
+int hrf_bbox_train_supported(const hrf_bbox_train_cfg_t* cfg, int B, int R, int Gmax);
+long hrf_bbox_train_workspace_bytes(const hrf_bbox_train_cfg_t* cfg, int B, int R, int Gmax);
+int hrf_bbox_targets(const hrf_bbox_train_cfg_t* cfg, int B, int R, const float* rois_in, const int* first, const int* count,
+                     int range_stride, const float* gt, const int* gt_labels, const int* gt_count, int Gmax, const unsigned* keys,
+                     const unsigned* rng_state, int stage, float* rois_s, int* labels, float* bbox_targets, int* src, int* counts,
+                     int* assigned, float* max_iou, void* stream);
+int hrf_bbox_loss(const hrf_bbox_train_cfg_t* cfg, int B, const float* out, int ld, const int* labels, const float* bbox_targets,
+                  const int* counts, void* workspace, long workspace_bytes, float* d_out, int ld_d, float* losses,
+                  unsigned* rng_state, void* stream);
 /* the same gather for EVERY fused layer of a step in one launch: seg = nseg rows of 5 longs on the device {offset (floats) of the
  * layer's ds_plane in `planes`, windows, heads, address of its drpb accumulator, copy_stride}; max_nwin / max_heads = the
  * largest of the rows (launch geometry).                                                                               */

@@ -20,7 +20,9 @@ extern "C" {
  * 36 = wave-group form of hrf_attn_block_fwd (0 = the dispatcher's choice, 1 / 2 / 4 = that many groups of four waves per window;
  * a launch of a width that is not built for the forced form returns HRF_ERR_ARG), 37 = a QUERY, not a status: returns the form a
  * forward of width `value` takes now (0: the forced form is not built for it), 44 = hrf_rpn_assign / hrf_rpn_loss return after
- * their first `value` launches (1..6; 0 = all: incomplete outputs - tools/rpn_loss_cost.py times the launches one by one). */
+ * their first `value` launches (1..6; 0 = all: incomplete outputs - tools/rpn_loss_cost.py times the launches one by one),
+ * 48 = hrf_bbox_targets returns after its first launch (value 1) / hrf_bbox_loss after its first launch (value 3); 0 = all
+ * (incomplete outputs - tools/roi_loss_cost.py). */
 int hrf_debug_knob(int key, int value);
 
 /* hrf_debug_knob(7, 1): HIP-event durations of the grouped weight-gradient launches of eager steps, aggregated per kernel
