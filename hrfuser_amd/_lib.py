@@ -78,7 +78,7 @@ def _ptr(t):
 
 _RAW_RETURN = ('hrf_conv3_wgrad_wide_scratch', 'hrf_conv_bwd_weight_scratch', 'hrf_conv3x_pack_size', 'hrf_conv3x_supported', 'hrf_conv_bwd_data_weight_supported', 'hrf_conv_fwd_split_scratch', 'hrf_wgrad_group_report', 'hrf_attn_block_supported', 'hrf_attn_block_bwd_supported', 'hrf_window_attn_proj_supported', 'hrf_group_count',
                'hrf_ffn_eval_supported', 'hrf_bottleneck_eval_supported', 'hrf_roi_align_supported', 'hrf_fuse_sum_bwd_supported', 'hrf_get_deterministic', 'hrf_det_bins_bytes', 'hrf_conv3_bf16x3_supported', 'hrf_grad_sumsq_parts',
-               'hrf_rpn_supported', 'hrf_rpn_workspace_bytes', 'hrf_nms_workspace_bytes', 'hrf_rpn_train_supported', 'hrf_rpn_train_workspace_bytes', 'hrf_fc_workspace_bytes', 'hrf_bbox_detect_workspace_bytes',
+               'hrf_rpn_supported', 'hrf_rpn_workspace_bytes', 'hrf_nms_workspace_bytes', 'hrf_rpn_train_supported', 'hrf_rpn_train_workspace_bytes', 'hrf_fc_workspace_bytes', 'hrf_fc_bwd_workspace_bytes', 'hrf_bbox_detect_workspace_bytes',
                'hrf_bbox_train_supported', 'hrf_bbox_train_workspace_bytes')       # return a value, not a status
 _ERR = {1: 'HRF_ERR_ARG (bad argument)', 2: 'HRF_ERR_LAUNCH (kernel launch failed)'}
 
@@ -130,7 +130,7 @@ class Lib:
         self._fns = {}
         for name, args in self.protos.items():
             fn = getattr(self._dll, name)          # AttributeError if a declared symbol is missing
-            fn.restype = ctypes.c_long if name in ('hrf_conv3_wgrad_wide_scratch', 'hrf_conv_bwd_weight_scratch', 'hrf_conv3x_pack_size', 'hrf_conv_fwd_split_scratch', 'hrf_wgrad_group_report', 'hrf_group_count', 'hrf_det_bins_bytes', 'hrf_grad_sumsq_parts', 'hrf_rpn_workspace_bytes', 'hrf_nms_workspace_bytes', 'hrf_rpn_train_workspace_bytes', 'hrf_fc_workspace_bytes', 'hrf_bbox_detect_workspace_bytes', 'hrf_bbox_train_workspace_bytes') else ctypes.c_int
+            fn.restype = ctypes.c_long if name in ('hrf_conv3_wgrad_wide_scratch', 'hrf_conv_bwd_weight_scratch', 'hrf_conv3x_pack_size', 'hrf_conv_fwd_split_scratch', 'hrf_wgrad_group_report', 'hrf_group_count', 'hrf_det_bins_bytes', 'hrf_grad_sumsq_parts', 'hrf_rpn_workspace_bytes', 'hrf_nms_workspace_bytes', 'hrf_rpn_train_workspace_bytes', 'hrf_fc_workspace_bytes', 'hrf_fc_bwd_workspace_bytes', 'hrf_bbox_detect_workspace_bytes', 'hrf_bbox_train_workspace_bytes') else ctypes.c_int
             fn.argtypes = [ct for ct, _ in args]
             self._fns[name] = self._wrap(name, fn, args)
         if os.environ.get('HRF_DETERMINISTIC', '0') == '1':       # initial state of the deterministic mode (include/hrfuser_hip.h)

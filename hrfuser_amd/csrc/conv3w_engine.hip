@@ -972,3 +972,4 @@ extern "C" __attribute__((visibility("hidden"))) int hrf_conv3w_knob(int key, in
 }
 
 #include "hrf_fc.h"
+#include "hrf_fc_bwd.h"

@@ -114,6 +114,53 @@ class FeatureExtractor(nn.Module):
             raise ValueError('FeatureExtractor.roi_loss: built without an rpn_head')
         return self._roi_losses(x, self.rpn_head(x), img, gt_bboxes, gt_labels, img_metas, proposal_cfg)
 
+    def roi_loss_backward(self, img, gt_bboxes, gt_labels, img_metas=None, lidar_img=None, radar_img=None, gated_img=None, proposal_cfg=None,
+                          pyramid_grads=None):
+        """`roi_loss` with its backward, on the explicit tapes: backbone tape -> neck tape -> rpn_head + proposals (no_grad) ->
+        CascadeRoIHead.losses_nhwc on the neck's ctx -> neck backward -> backbone backward - the tape calls of
+        ExtractTrainer._step_impl with the RoI losses in place of the synthetic cotangents.  Returns roi_loss's dict (the same
+        values) and leaves d (sum of the s{i}.loss_cls / s{i}.loss_bbox) in the two flat gradient arenas (added to their
+        contents, like .backward()) and in .grad of the head parameters.  No optimizer step, no gradient through the RPN head.
+        pyramid_grads: a list that receives a copy of the gradient on every pyramid level (NHWC; None for an unused level)."""
+        if getattr(self, 'roi_head', None) is None or getattr(self, 'rpn_head', None) is None or not self.with_neck:
+            raise ValueError('FeatureExtractor.roi_loss_backward: built without a neck / rpn_head / roi_head')
+        from .roi_head import pack_gt_labels
+        from .rpn import _shapes, pack_gts
+        mods = combine_mod_imgs(lidar_img, radar_img, gated_img) or []
+        if img_metas is None:
+            img_metas = [dict(img_shape=tuple(img.shape[-2:]), pad_shape=tuple(img.shape[-2:]))] * img.shape[0]
+        dev = img.device
+        gt, gt_count = pack_gts(gt_bboxes, dev)
+        shp = _shapes([m['img_shape'] for m in img_metas], img.shape[0], dev)
+        vals = self._roi_loss_backward(img, mods, gt, pack_gt_labels(gt_labels, dev, gt.shape[1]), gt_count, shp, proposal_cfg, pyramid_grads)
+        out = {}
+        for i in range(self.roi_head.num_stages):
+            out[f's{i}.loss_cls'], out[f's{i}.acc'], out[f's{i}.loss_bbox'] = vals[i, 0], vals[i, 2], vals[i, 1]
+        return out
+
+    def _roi_loss_backward(self, img, mods, gt, gt_labels, gt_count, shp, proposal_cfg=None, pyramid_grads=None):
+        """the device part of roi_loss_backward on packed ground truths (rpn.pack_gts, roi_head.pack_gt_labels) and the (B,2) shape
+        tensor: fixed shapes, nothing read on the host - capturable -> the (num_stages, 3) values of CascadeRoIHead.losses"""
+        net, neck = self.backbone, self.neck
+        cb, outs, _ = net._execute((img,) + tuple(mods), True)
+        en = neck._engine()
+        en.ready(img.device)
+        en.begin_forward(neck.training)
+        cn = R.Ctx(neck, neck.training, True)
+        with torch.no_grad():
+            srcs = [R.Act(o.t, True) for o in outs]              # the backbone's NHWC maps, in place
+            pyr = neck._run(cn, srcs)
+            x = [p.t.permute(0, 3, 1, 2) for p in pyr]
+            _, count, rois = self.rpn_head.proposals(*self.rpn_head(x), shp, proposal_cfg)
+            vals, _ = self.roi_head.losses_nhwc(cn, pyr, rois, count, gt, gt_labels, gt_count, shp)
+        cn.run_backward()
+        if pyramid_grads is not None:
+            pyramid_grads.extend(None if p.grad is None else p.grad.clone() for p in pyr)
+        for o, s_ in zip(outs, srcs):
+            o.grad = s_.grad
+        cb.run_backward()
+        return vals
+
     def losses(self, img, gt_bboxes, gt_labels, img_metas=None, lidar_img=None, radar_img=None, gated_img=None, proposal_cfg=None):
         """two_stage.py:163-177: the RPN's dict (loss_rpn_cls / loss_rpn_bbox per level) and the RoI head's (s{i}.*) merged, from
         ONE pass through the backbone, the neck and the RPN head."""

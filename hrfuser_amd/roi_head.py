@@ -3,7 +3,7 @@ reference config (configs/_base_/models/cascade_rcnn_hrfuser_fpn_*_fusion.py:148
 
 Drop-ins for mmdet's `Shared2FCBBoxHead` (mmdet/models/roi_heads/bbox_heads/convfc_bbox_head.py, bbox_head.py) and
 `CascadeRoIHead` (cascade_roi_head.py:288-400): same registry names, constructor keywords and state-dict keys
-(`bbox_head.{i}.shared_fcs.{0,1}.*`, `fc_cls.*`, `fc_reg.*`).  The forward is eval only, fp32, no tape; with a `train_cfg` (a list of
+(`bbox_head.{i}.shared_fcs.{0,1}.*`, `fc_cls.*`, `fc_reg.*`).  `forward` / `detect` / `losses` are fp32 without a tape; with a `train_cfg` (a list of
 one train_cfg.rcnn dict per stage) the RoI head computes mmdet's per-stage losses and their gradient on each stage's head output,
 without one `loss` / `get_targets` / `forward_train` raise.
 
@@ -25,7 +25,14 @@ without one `loss` / `get_targets` / `forward_train` raise.
                stage's proposals - the refined rows without the gts - are a row range read from the device `counts`.  Fixed shapes, no
                host read: capturable.  `forward_train` wraps it into mmdet's dict; `Shared2FCBBoxHead.loss` gives the values a grad_fn.
 
-Functional entries underneath: `fc`, `bbox_refine`, `bbox_detect`, `bbox_targets`, `bbox_loss`.  There is no CPU fallback.
+  Shared2FCBBoxHead.run_train / run_backward / forward_autograd   the same forward with the activations kept, and its backward
+               (csrc/hrf_fc_bwd.h): per layer hrf_fc_bwd_weight (dw += dy^T x, db += sum dy) and hrf_fc_bwd_data (dx = dy w with the
+               ReLU mask of the layer below in the epilogue), exact fp32 MFMA, no atomics; .grad lands on the eight parameters.
+  CascadeRoIHead.losses_nhwc  `losses` on the explicit tape (runtime.Ctx): the same values, and per stage the closures that carry the
+               loss gradient through the head and the RoIAlign adjoint into the pyramid's act.grad.
+
+Functional entries underneath: `fc`, `fc_backward_data`, `fc_backward_weight`, `bbox_refine`, `bbox_detect`, `bbox_targets`, `bbox_loss`.
+There is no CPU fallback.
 """
 import os
 
@@ -33,6 +40,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from . import runtime as R
 from .registry import HEADS, ROI_EXTRACTORS
 from .roi import POOLED, _nhwc, roi_forward
 from .rpn import MAX_GT, MAX_PRE, _shapes, pack_gts, rng_state
@@ -93,6 +101,48 @@ def fc(x, wp, bias, N, relu=False, out=None, route=None, stream=None, consts=Non
     ws = torch.empty((need,), device=x.device, dtype=torch.uint8) if need > 0 else None
     L.hrf_fc(x, ldX, wp, bias, out, ldY, int(bool(relu)), M, K, N, ws, need, s)
     return out
+
+
+def _rows(t, cols, what):
+    if t.dim() != 2 or t.shape[1] < cols or t.dtype != torch.float32 or t.stride(1) != 1:
+        raise ValueError(f'{what} must be fp32 (M, >= {cols}) rows, got {tuple(t.shape)} {t.dtype} strides {tuple(t.stride())}')
+    return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def fc_bwd_workspace(M, K, N, dev):
+    """the workspace one layer's two backward launches share (hrf_fc_bwd_workspace_bytes), or None"""
+    need = _lib.lib().hrf_fc_bwd_workspace_bytes(M, K, N)
+    return torch.empty((need,), device=dev, dtype=torch.uint8) if need > 0 else None
+
+
+def fc_backward_data(dy, wp, K, mask=None, out=None, workspace=None, stream=None):
+    """hrf_fc_bwd_data: dy (M, >= N) rows (the N leading columns are read), wp the packed (N, K) weight, mask (M, K) the forward
+    output of the ReLU layer below or None -> dx (M, K) = where(mask <= 0, 0, dy @ w): the dy of the layer below"""
+    L = _lib.lib()
+    M, N = dy.shape[0], wp.numel() // K
+    ldDY = _rows(dy, N, 'fc_backward_data: dy')
+    if out is None:
+        out = torch.empty((M, K), device=dy.device, dtype=torch.float32)
+    ldDX = _rows(out, K, 'fc_backward_data: out')
+    ldM = 0 if mask is None else _rows(mask, K, 'fc_backward_data: mask')
+    if workspace is None:
+        workspace = fc_bwd_workspace(M, K, N, dy.device)
+    L.hrf_fc_bwd_data(dy, ldDY, wp, K, mask, ldM, out, ldDX, M, K, N, workspace, 0 if workspace is None else workspace.numel(), _stream(stream))
+    return out
+
+
+def fc_backward_weight(x, dy, N, dw, db=None, accumulate=False, workspace=None, stream=None):
+    """hrf_fc_bwd_weight: x (M, K) rows, dy (M, >= N) rows -> dw (N, K) (+)= dy[:, :N].T @ x, db (N,) (+)= dy[:, :N].sum(0)"""
+    L = _lib.lib()
+    M, K = x.shape
+    ldX, ldDY, ldDW = _rows(x, K, 'fc_backward_weight: x'), _rows(dy, N, 'fc_backward_weight: dy'), _rows(dw, K, 'fc_backward_weight: dw')
+    if dw.shape[0] != N or (db is not None and (db.shape != (N,) or db.dtype != torch.float32 or not db.is_contiguous())):
+        raise ValueError(f'fc_backward_weight: dw ({N}, {K}) and db ({N},) fp32 are needed, got {tuple(dw.shape)}')
+    if workspace is None:
+        workspace = fc_bwd_workspace(M, K, N, x.device)
+    L.hrf_fc_bwd_weight(x, ldX, dy, ldDY, dw, ldDW, db, int(bool(accumulate)), M, K, N, workspace, 0 if workspace is None else workspace.numel(),
+                        _stream(stream))
+    return dw, db
 
 
 def bbox_refine(rois, deltas, stds, img_shapes, B, out=None, stream=None):
@@ -307,6 +357,26 @@ class _BboxLossFn(torch.autograd.Function):
         return None, None, None, None, d[:, :nc + 1] * gl[0], d[:, nc + 1:nc + 5] * gl[1]
 
 
+class _HeadFn(torch.autograd.Function):
+    """torch.autograd bridge of Shared2FCBBoxHead.forward_autograd over run_train / run_backward.  The parameters are not autograd
+    inputs: run_backward adds their gradients into .grad itself."""
+
+    @staticmethod
+    def forward(fctx, head, nhwc, x):
+        out, saved = head.run_train(x.detach().float().contiguous().reshape(x.shape[0], -1), nhwc=nhwc)
+        fctx.hrf = (head, saved, tuple(x.shape))
+        return out
+
+    @staticmethod
+    def backward(fctx, gout):
+        head, saved, shape = fctx.hrf
+        g = gout.float()
+        if g.stride(1) != 1:
+            g = g.contiguous()
+        dx = head.run_backward(saved, g, need_dx=fctx.needs_input_grad[2])
+        return None, None, (None if dx is None else dx.reshape(shape))
+
+
 def _not_built(who, key, value, why):
     return NotImplementedError(f'{who} on the HIP engine: {key}={value!r} is not built ({why})')
 
@@ -458,6 +528,91 @@ class Shared2FCBBoxHead(nn.Module):
             raise ValueError(f'Shared2FCBBoxHead.forward: expected (K, {want[0]}, {want[1]}, {want[2]}) ({layout}), got {tuple(x.shape)}')
         with torch.no_grad():
             out = self.run(x.detach().contiguous().reshape(x.shape[0], -1), nhwc=layout == 'nhwc')
+        return out[:, :nc + 1], out[:, nc + 1:nc + 5]
+
+    # -- training: the same forward with what the backward needs kept, and the backward (csrc/hrf_fc_bwd.h) -----------------
+    def run_train(self, x2d, nhwc=False, stream=None):
+        """`run` (the same launches, the same bits) -> (out, saved): saved keeps x2d, the two hidden activations and the packed
+        weights the forward used, for `run_backward`"""
+        L = _lib.lib()
+        if L.require_cuda and not x2d.is_cuda:
+            raise _lib.HRFuserHipError(f'Shared2FCBBoxHead: tensor on {x2d.device}; the HIP path has no CPU fallback')
+        dev = x2d.device
+        pk = self._packed(dev)
+        if x2d.dim() != 2 or x2d.shape[1] != pk['Kin'] or x2d.dtype != torch.float32 or not x2d.is_contiguous():
+            raise ValueError(f'Shared2FCBBoxHead: features must be contiguous fp32 (K, {pk["Kin"]}), got {tuple(x2d.shape)} {x2d.dtype}')
+        F = self.fc_out_channels
+        w1 = self._w1(pk, dev, nhwc)
+        h1 = fc(x2d, w1, pk['b1'], F, True, stream=stream, consts=pk['consts'])
+        h2 = fc(h1, pk['w2'], pk['b2'], F, True, stream=stream, consts=pk['consts'])
+        out = fc(h2, pk['w3'], pk['b3'], self.out_pitch, False, stream=stream)
+        return out, dict(x=x2d, h1=h1, h2=h2, w1=w1, w2=pk['w2'], w3=pk['w3'], nhwc=bool(nhwc))
+
+    def _grad_pair(self, lin, dev):
+        """(weight.grad, bias.grad, accumulate) of a Linear: existing gradients are added to, missing ones created"""
+        w, b = lin.weight, lin.bias
+        fresh = w.grad is None and b.grad is None
+        for p in (w, b):
+            if p.grad is None:
+                p.grad = torch.empty_like(p, memory_format=torch.contiguous_format) if fresh else torch.zeros_like(p, memory_format=torch.contiguous_format)
+            if p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.device != dev:
+                raise _not_built('Shared2FCBBoxHead', 'parameter .grad', (p.grad.dtype, str(p.grad.device)), f'contiguous fp32 on {dev}')
+        return w.grad, b.grad, not fresh
+
+    def run_backward(self, saved, d_out, need_dx=True, stream=None):
+        """The backward of `run_train`: d_out (K, >= out_pitch) rows, the gradient on the padded output (hrf_bbox_loss's d_out) ->
+        the gradient on x2d (K, 49 * C) in x2d's column order, or None (need_dx False).  Six launches of the two backward kernels -
+        w3 weight / data, w2 weight / data, w1 weight / (data) - plus the bias sums; each data gradient carries the ReLU mask of the
+        layer below.  Adds into .grad of the eight parameters, in the parameters' own shape and order (created when None): rows
+        [0, num_classes] of the padded last layer are fc_cls, the next four fc_reg, the padding rows go nowhere; fc1's gradient
+        taken on (y, x, c) feature columns is brought back to (c, y, x) by hrf_fc_bwd_cols."""
+        L = _lib.lib()
+        x, h1, h2 = saved['x'], saved['h1'], saved['h2']
+        dev, M = x.device, x.shape[0]
+        F, Kin, P, nc = self.fc_out_channels, self.in_channels * self.roi_feat_area, self.out_pitch, self.num_classes
+        if d_out.dim() != 2 or d_out.shape[0] != M or d_out.shape[1] < P or d_out.dtype != torch.float32 or d_out.stride(1) != 1 or d_out.device != dev:
+            raise ValueError(f'Shared2FCBBoxHead.run_backward: d_out must be fp32 ({M}, >= {P}) rows on {dev}, got {tuple(d_out.shape)} {d_out.dtype}')
+        s = _stream(stream)
+        # last layer: one padded gradient, its rows handed to the two parameters
+        ws = fc_bwd_workspace(M, F, P, dev)
+        dw3, db3 = torch.empty((P, F), device=dev), torch.empty((P,), device=dev)
+        fc_backward_weight(h2, d_out, P, dw3, db3, False, ws, s)
+        for lin, lo, hi in ((self.fc_cls, 0, nc + 1), (self.fc_reg, nc + 1, nc + 5)):
+            gw, gb, acc = self._grad_pair(lin, dev)
+            n = gw.numel()
+            L.hrf_scale_add(dw3[lo:hi], None, 1.0, None, 1, gw if acc else None, None, gw, n, 1, s)
+            L.hrf_scale_add(db3[lo:hi], None, 1.0, None, 1, gb if acc else None, None, gb, hi - lo, 1, s)
+        d2 = fc_backward_data(d_out, saved['w3'], F, h2, None, ws, s)
+        # fc2
+        ws = fc_bwd_workspace(M, F, F, dev)
+        gw, gb, acc = self._grad_pair(self.shared_fcs[1], dev)
+        fc_backward_weight(h1, d2, F, gw, gb, acc, ws, s)
+        d1 = fc_backward_data(d2, saved['w2'], F, h1, None, ws, s)
+        # fc1
+        ws = fc_bwd_workspace(M, Kin, F, dev)
+        gw, gb, acc = self._grad_pair(self.shared_fcs[0], dev)
+        if saved['nhwc']:
+            tmp, tmpb = torch.empty((F, Kin), device=dev), torch.empty((F,), device=dev)
+            fc_backward_weight(x, d1, F, tmp, tmpb, False, ws, s)
+            L.hrf_fc_bwd_cols(tmp, Kin, gw, Kin, int(acc), F, self.in_channels, self.roi_feat_area, s)
+            L.hrf_scale_add(tmpb, None, 1.0, None, 1, gb if acc else None, None, gb, F, 1, s)
+        else:
+            fc_backward_weight(x, d1, F, gw, gb, acc, ws, s)
+        if not need_dx:
+            return None
+        return fc_backward_data(d1, saved['w1'], Kin, None, None, ws, s)
+
+    def forward_autograd(self, x, layout=None):
+        """`forward` with a grad_fn on (cls_score, bbox_pred): backward runs `run_backward`, which leaves the parameter gradients
+        in .grad and delivers x.grad in x's layout.  With `loss` and SingleRoIExtractor.forward a .backward() on s{i}.loss_*
+        reaches the pyramid."""
+        C, nc = self.in_channels, self.num_classes
+        if layout is None:
+            layout = 'nchw' if tuple(x.shape[1:]) == (C, POOLED, POOLED) else 'nhwc'
+        want = (C, POOLED, POOLED) if layout == 'nchw' else (POOLED, POOLED, C)
+        if x.dim() != 4 or tuple(x.shape[1:]) != want:
+            raise ValueError(f'Shared2FCBBoxHead.forward_autograd: expected (K, {want[0]}, {want[1]}, {want[2]}) ({layout}), got {tuple(x.shape)}')
+        out = _HeadFn.apply(self, layout == 'nhwc', x)
         return out[:, :nc + 1], out[:, nc + 1:nc + 5]
 
     def _no_train_cfg(self, what):
@@ -746,6 +901,65 @@ class CascadeRoIHead(nn.Module):
                 if i < S - 1:
                     rois = bbox_refine(rois_s, out[:, nc + 1:nc + 5], hd.target_stds, shp, B)
                     first, count = counts[:, 4], counts[:, 5]      # the sampled gts lead every image: the pos_is_gt filter is a row range
+        return out_losses, grads
+
+    def losses_nhwc(self, *args, **kwargs):
+        """`losses` on the tape.  Signature (ctx, acts, rois, count, gt, gt_labels, gt_count, img_shapes, stages=None, keys=None): acts
+        the runtime.Act's of the pyramid (HRFPN._run's outputs, NHWC, read in place), the rest as `losses` -> what `losses`
+        returns, the same bits for the same inputs and keys (the same launches in the same order).  With a recording ctx every
+        stage pushes its backward: the features come through SingleRoIExtractor.extract_nhwc (whose closure is the RoIAlign
+        adjoint) and the head's closure runs Shared2FCBBoxHead.run_backward on the stage's d_out, which fills the features'
+        gradient.  ctx.run_backward() then adds into act.grad of the used levels and into .grad of the head parameters.  No
+        gradient flows through the boxes between the stages (cascade_roi_head.py:269 refines them under no_grad).  Fixed
+        shapes, no host read, no synchronisation: forward and backward are capturable.  The FC backward is free of atomics;
+        hrf_roi_align_bwd is not, and stays refused in deterministic mode."""
+        if self.train_cfg is None:
+            raise self._no_train_cfg('losses_nhwc')
+        return self._losses_nhwc(*args, **kwargs)
+
+    def _losses_nhwc(self, ctx, acts, rois, count, gt, gt_labels, gt_count, img_shapes, stages=None, keys=None, out_layout=1):
+        acts = list(acts)
+        B, dev = acts[0].t.shape[0], acts[0].t.device
+        rois = rois.detach().float().contiguous()
+        if rois.dim() != 2 or rois.shape[1] != 5 or rois.shape[0] % B != 0 or rois.shape[0] == 0:
+            raise ValueError(f'CascadeRoIHead.losses_nhwc: rois must be (B * R, 5) with R >= 1, got {tuple(rois.shape)} for B = {B}')
+        shp = _shapes(img_shapes, B, dev)
+        nc, S = self.bbox_head[0].num_classes, self.num_stages
+        rng = None if keys is not None else self.rng(dev)
+        out_losses = torch.empty((S, 3), device=dev, dtype=torch.float32)
+        grads, first, s = [], None, ctx.stream
+        with torch.no_grad():
+            for i in range(S):
+                ex, hd = self.bbox_roi_extractor[i], self.bbox_head[i]
+                if len(acts) < ex.num_inputs:
+                    raise ValueError(f'CascadeRoIHead: {ex.num_inputs} strides, {len(acts)} maps')
+                cfg = rcnn_train_cfg_struct(**self._stage_train[i])
+                t = bbox_targets(rois, gt, gt_labels, gt_count, cfg, first, count, keys=None if keys is None else keys[i], rng=rng, stage=i, stream=s)
+                rois_s, labels, targets, _, counts = t[:5]
+                # (y, x, c) feature columns, as `losses` runs them: the values are the same bits; out_layout 0 is the A/B of
+                # tools/fc_bwd_cost.py (fc1's gradient then needs no hrf_fc_bwd_cols)
+                feat = ex.extract_nhwc(ctx, acts, rois_s, out_layout=out_layout)
+                out, saved = hd.run_train(feat.t.reshape(feat.t.shape[0], -1), nhwc=out_layout == 1, stream=s)
+                _, d = bbox_loss(out, labels, targets, counts, cfg, rng=rng if i == S - 1 else None, losses=out_losses[i], stream=s)
+                grads.append(d)
+
+                def bwd(hd=hd, saved=saved, d=d, feat=feat, used=acts[:ex.num_inputs]):
+                    dx = hd.run_backward(saved, d, need_dx=any(a.needs_grad for a in used), stream=ctx.stream)
+                    if dx is not None:
+                        feat.grad = dx.reshape(feat.t.shape)
+                ctx.push(bwd)
+                if stages is not None:
+                    stages.append(dict(rois=rois, first=first, count=count, targets=t, out=out, d_out=d, cfg=cfg, feat=feat))
+                if i < S - 1:
+                    rois = bbox_refine(rois_s, out[:, nc + 1:nc + 5], hd.target_stds, shp, B, stream=s)
+                    first, count = counts[:, 4], counts[:, 5]
+        nmax = max(ex.num_inputs for ex in self.bbox_roi_extractor)
+
+        def bwd_first():                                            # pushed last: the first closure of this part of the tape
+            for a in acts[:nmax]:                                   # the RoIAlign adjoint adds into act.grad: zeroed maps where there is none yet
+                if a.needs_grad and a.grad is None:
+                    a.grad = R._keep(torch.zeros_like(a.t))
+        ctx.push(bwd_first)
         return out_losses, grads
 
     def forward_train(self, *args, **kwargs):

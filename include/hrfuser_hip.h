@@ -614,6 +614,35 @@ long hrf_bbox_detect_workspace_bytes(int B, int R, int num_classes);
 int hrf_bbox_detect(const hrf_bbox_det_t* d, void* workspace, long workspace_bytes, float* dets, int* labels, int* count_out,
                     void* stream);
 
+/* ---- Backward of hrf_fc's layer (csrc/hrf_fc_bwd.h, part of csrc/conv3w_engine.hip) ------------------------------------------------
+ * The gradients of y = act(bias + x w^T) for the three linear layers of Shared2FCBBoxHead in training.  Exact fp32 MFMA, hrf_fc's
+ * block tile; no atomics, no arrival counters (the same bits from run to run and in deterministic mode), nothing read on the host,
+ * no allocation, no synchronisation: capturable.  All pointers fp32; K % 16 == 0, N % 16 == 0, N <= 65536, 0 <= M <= 2^24.
+ *
+ * hrf_fc_bwd_data  dx[m][k] = (mask != null && mask[m][k] <= 0) ? +0 : sum_n dy[m][n] * w[n][k].
+ *   dy [M] rows of pitch ldDY >= N, w [N] rows of pitch ldW >= K (what hrf_fc_pack writes, pitch K), mask [M] rows of pitch ldMask
+ *   >= K or null: the FORWARD OUTPUT of the layer below when that layer ran with relu == 1, so that dx is already that layer's dy.
+ *   The mask is a select (torch's threshold_backward): a masked element is +0 even where the sum is NaN / Inf, and a NaN in the
+ *   mask lets the gradient through.  dx [M] rows of pitch ldDX >= K.  Pad columns are never read or written.
+ * hrf_fc_bwd_weight  dw[n][k] (+)= sum_m dy[m][n] * x[m][k];  db[n] (+)= sum_m dy[m][n]  (db nullable; one more small launch).
+ *   x [M] rows of pitch ldX >= K, dw [N] rows of pitch ldDW >= K, accumulate 0 (overwrite) or 1 (add to the contents).
+ * Where the output has too few 128 x 128 tiles the reduction (N resp. M) is split over blocks - a function of (M, K, N) alone - and
+ * the partial tiles go through slots of `workspace`, folded in slot order by a second launch.  hrf_fc_bwd_workspace_bytes(M, K, N):
+ * the larger of the two entries' needs (0 when neither splits or the shape is refused); caller-owned, contents irrelevant, 16-byte
+ * aligned; one buffer serves both calls of a layer.
+ * M == 0: HRF_OK; hrf_fc_bwd_weight with accumulate == 0 still writes zeros to dw / db.
+ * REFUSED (HRF_ERR_ARG before any launch): K % 16 != 0, N % 16 != 0, K / N < 1, M < 0, a null dy / w / dx / x / dw, a pitch below its
+ * row length, accumulate not 0 / 1, a workspace that is null or too small when one is needed.
+ * hrf_fc_bwd_cols  dst[n][c * A + a] (+)= src[n][a * C + c], n < N: a weight gradient taken on (y, x, c)-ordered feature columns
+ *   ([K][7][7][C] RoI features, A = 49) into the parameter's (c, y, x) order.  Rows of pitch ldSrc / ldDst >= A * C; one launch.
+ *   REFUSED: null pointers, N < 0, C / A < 1, a pitch below A * C, accumulate not 0 / 1, A * (C + 1) floats above 64 KB of LDS. */
+long hrf_fc_bwd_workspace_bytes(long M, int K, int N);
+int hrf_fc_bwd_data(const float* dy, int ldDY, const float* w, int ldW, const float* mask, int ldMask, float* dx, int ldDX, long M, int K,
+                    int N, void* workspace, long workspace_bytes, void* stream);
+int hrf_fc_bwd_weight(const float* x, int ldX, const float* dy, int ldDY, float* dw, int ldDW, float* db, int accumulate, long M, int K, int N,
+                      void* workspace, long workspace_bytes, void* stream);
+int hrf_fc_bwd_cols(const float* src, int ldSrc, float* dst, int ldDst, int accumulate, int N, int C, int A, void* stream);
+
 /* ---- Cascade RoI head training targets and loss (csrc/hrf_bbox_train.h, part of csrc/pointwise.hip) -----------------------------
  * One stage of train_cfg.rcnn[i]: what CascadeRoIHead.forward_train does per stage between the proposals and the loss values
  * (mmdet/models/roi_heads/cascade_roi_head.py:191-286, bbox_heads/bbox_head.py:122-313, core/bbox/assigners/max_iou_assigner.py
